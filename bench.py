@@ -24,7 +24,11 @@ N GPUs : one process per GPU, every rank owns its own 4096 scenes (weak scaling,
          devices are visible; under torchrun (the driver's form) --gpus must equal WORLD_SIZE.  `n_gpus` in
          the output is the number of ranks that reported, on distinct devices.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects:
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints ONE JSON line on rank 0: `metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step` (wall clock of one timed step), `n_gpus`, `steps`, `warmup` and `config` (what was
+timed).  `--dump-outputs DIR` also writes what the timed path returned in its last step as DIR/<name>.npy (see `dump_outputs`).
+`--full` adds everything else the line used to carry - the objects below, each measured or checked after the timed region:
+  per_rank / host_us_per_step / host_bound_ceiling - every rank's own clock, kernel times and the host time to issue a step.
   roofline      - dominant kernel (the forward PDIPM kernel).  `achieved` / `frac` = the FLOPs the kernel really EXECUTES
                   (lcp_physics_amd/flops.py, with the iteration counts the kernel reports) divided by its average launch
                   duration - HIP events on the launch stream around >= 128 eager launches right after the timed region
@@ -62,6 +66,8 @@ sys.path.insert(0, ROOT)
 
 PEAK_TFLOPS = {"f64": 78.6, "f32": 157.3}   # MI355X FP64 / FP32 vector = matrix rates (datasheet; MI355X_MICROARCH.md lists FP32)
 HBM_PEAK_GBS = 8000.0
+DUMP_MAX_BYTES = 64 * 10 ** 6    # --dump-outputs: all files together (64 MB)
+DUMP_SEED = 20240917             # ... and the seed of the scene sample taken when the batch's outputs are larger
 
 
 def parse(argv=None):
@@ -101,7 +107,15 @@ def parse(argv=None):
     ap.add_argument("--sustain", type=float, default=1.0, help="seconds of the untimed sustained loop after the timed steps (0 = off)")
     ap.add_argument("--share-devices", action="store_true",
                     help="TESTING AID: let several ranks use one GPU (gloo instead of RCCL); the line then says devices_used < n_gpus")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything besides the headline figure: roofline (event-timed kernels), per-rank and host-issue "
+                         "figures, the sustained loop, companions, cpu_baseline / cpu_reference and parity (off: the plain run times the steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32 / float64, "
+                         "at most %d MB: a fixed, seeded sample of the scenes when the whole batch is larger)" % (DUMP_MAX_BYTES // 10 ** 6))
     a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if a.config == 1:
         a.batch, a.nbox, a.fwd_only = a.batch or 1024, a.nbox or 2, True
     elif a.config == 3:
@@ -151,6 +165,29 @@ def timed_steps(work, steps, warmup, sync):
     return wall, own
 
 
+def dump_outputs(outputs, out_dir):
+    """--dump-outputs: `outputs` = {name: tensor with the scenes along dim 0} -> out_dir/<name>.npy; float32 stays float32, everything
+    else (fp64, the int32 iteration counts and status words) is written as float64.  When the batch's outputs together exceed
+    DUMP_MAX_BYTES, every file holds the same fixed sample of scenes (DUMP_SEED, ascending scene order): the same arguments give the same
+    scenes, inputs and sample from run to run, so two builds can be compared file by file.  Returns the names written."""
+    import numpy as np
+    arrs = {k: v.detach().cpu() for k, v in outputs.items() if v is not None}
+    arrs = {k: v if v.dtype == torch.float32 else v.double() for k, v in arrs.items()}
+    B = {v.shape[0] for v in arrs.values()}
+    assert len(B) == 1, "dump_outputs: every output has the scenes along dim 0"
+    B = B.pop()
+    per_scene = sum(v.element_size() * (v.numel() // max(1, B)) for v in arrs.values())
+    budget = DUMP_MAX_BYTES - 4096 * len(arrs)                     # (room for the .npy headers)
+    if per_scene * B > budget:
+        n = budget // per_scene
+        idx = torch.randperm(B, generator=torch.Generator().manual_seed(DUMP_SEED))[:n].sort().values
+        arrs = {k: v[idx] for k, v in arrs.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v.contiguous().numpy())
+    return sorted(arrs)
+
+
 def run_rank(args, make_work, device=None):
     """Everything one rank does.  `make_work(args, rank, device)` builds the workload (HipWorkload below; the CPU
     test of the N > 1 protocol passes a stand-in whose step launches nothing).  Returns the JSON object on rank 0."""
@@ -169,9 +206,11 @@ def run_rank(args, make_work, device=None):
     sync = torch.cuda.synchronize if is_gpu else (lambda: None)
     work = make_work(args, rank, dev)
     own_wall_all, own_wall = timed_steps(work, args.steps, args.warmup, sync)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(work.outputs(), args.dump_outputs)      # (before anything else launches: the last timed step's results)
     wall = shard.max_over_ranks(own_wall_all, device=rdev)
     # kernel durations: HIP events around eager launches, outside the timed region
-    samples = work.sample_kernels(args.event_samples) if hasattr(work, "sample_kernels") else None
+    samples = work.sample_kernels(args.event_samples) if (args.full and hasattr(work, "sample_kernels")) else None
     # how many ranks really ran, and on how many distinct devices
     reported = int(round(shard.sum_over_ranks(1.0, device=rdev)))
     dev_index = torch.device(dev).index or 0
@@ -182,31 +221,6 @@ def run_rank(args, make_work, device=None):
         raise SystemExit("bench.py: %d of %d ranks reported" % (reported, world))
     if is_gpu and devices_used != world and not args.share_devices:
         raise SystemExit("bench.py: %d ranks on %d distinct devices" % (world, devices_used))
-    # what a step costs THIS rank's host thread with the device idle in front of it: the launches of a few steps issued back to back, the
-    # clock stopped before the device is waited for.  With N ranks on one host these are N threads doing this concurrently; the step
-    # cannot go faster than the slowest of them issues it - `host_bound_ceiling` below is that bound in the metric's unit, so that a
-    # scaling result below 7 x at N = 8 can be read off the line: kernels slower (per_rank fwd_ms / bwd_ms) or hosts slower (host_us_per_step)
-    sync()
-    n_issue = 20 if is_gpu else 3
-    t0 = time.perf_counter()
-    for _ in range(n_issue):
-        work.step()
-    host_us = (time.perf_counter() - t0) / n_issue * 1e6
-    sync()
-    sustained = None
-    if args.sustain > 0:
-        sync()
-        t0, n = time.perf_counter(), 0
-        while True:
-            for _ in range(max(1, args.steps)):
-                work.step()
-            n += max(1, args.steps)
-            sync()
-            if time.perf_counter() - t0 >= args.sustain:
-                break
-        dt = time.perf_counter() - t0
-        sustained = {"seconds": dt, "steps": n, "value": work.units_per_step * world * n / dt, "unit": "sim steps/s",
-                     "note": "untimed-region repeat of the same step (this rank's clock), not the metric"}
     total_units = work.units_per_step * world * args.steps
     out = {
         "metric": work.metric_name(),
@@ -222,6 +236,58 @@ def run_rank(args, make_work, device=None):
         "dtype": args.compute,
         "data": "synthetic",
     }
+    if args.full:
+        out.update(full_figures(args, work, sync, samples, rank, world, dev_index, wall, own_wall, rdev, is_gpu))
+    else:
+        out.update(work.report(None, world))          # (the plain run: the workload's description, no roofline - nothing more is launched)
+    out["config"]["global_batch"] = work.units_per_step * world
+    out["config"]["parallelism"] = "scenes sharded x%d, no collectives" % world
+    out["config"]["control_plane"] = shard.control_plane()          # what carried the barriers / the MAX of the wall times
+    if is_gpu and devices_used != reported:
+        out["devices_used"] = devices_used
+    if args.full and rank == 0 and world == 1 and not args.no_companions and hasattr(work, "companions"):
+        out.update(work.companions(sync))
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
+        out.update(work.host_side_checks())
+    elif args.full and rank == 0:
+        out["cpu_baseline"] = None
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if world > 1:
+        import torch.distributed as dist
+        dist.destroy_process_group()
+    return out if rank == 0 else None
+
+
+def full_figures(args, work, sync, samples, rank, world, dev_index, wall, own_wall, rdev, is_gpu):
+    """--full, every rank, after the timed region: the host-issue probe, the sustained loop, the roofline (`work.report` with the
+    event-timed kernel samples) and the per-rank records.  Returns the objects to add to the line."""
+    from lcp_physics_amd import shard
+    # what a step costs THIS rank's host thread with the device idle in front of it: the launches of a few steps issued back to back, the
+    # clock stopped before the device is waited for.  With N ranks on one host these are N threads doing this concurrently; the step
+    # cannot go faster than the slowest of them issues it - `host_bound_ceiling` below is that bound in the metric's unit, so that a
+    # scaling result below 7 x at N = 8 can be read off the line: kernels slower (per_rank fwd_ms / bwd_ms) or hosts slower (host_us_per_step)
+    sync()
+    n_issue = 20 if is_gpu else 3
+    t0 = time.perf_counter()
+    for _ in range(n_issue):
+        work.step()
+    host_us = (time.perf_counter() - t0) / n_issue * 1e6
+    sync()
+    out = {}
+    if args.sustain > 0:
+        sync()
+        t0, n = time.perf_counter(), 0
+        while True:
+            for _ in range(max(1, args.steps)):
+                work.step()
+            n += max(1, args.steps)
+            sync()
+            if time.perf_counter() - t0 >= args.sustain:
+                break
+        dt = time.perf_counter() - t0
+        out["sustained"] = {"seconds": dt, "steps": n, "value": work.units_per_step * world * n / dt, "unit": "sim steps/s",
+                            "note": "untimed-region repeat of the same step (this rank's clock), not the metric"}
     rep_ = work.report(samples, world)                # (every rank: its own kernel timings go into `per_rank`)
     out.update(rep_)
     # per-rank record, so that an N > 1 line can be audited rank by rank: this rank's own wall clock over the timed region (the
@@ -245,25 +311,7 @@ def run_rank(args, make_work, device=None):
     out["host_bound_ceiling"] = {"value": work.units_per_step * world / (out["host_us_per_step"] * 1e-6), "unit": "sim steps/s",
                                  "note": "all ranks' units per step / the slowest rank's host time to ISSUE a step (its launches back to back, device not "
                                          "waited for): the value cannot exceed this however fast the kernels are"}
-    out["config"]["global_batch"] = work.units_per_step * world
-    out["config"]["parallelism"] = "scenes sharded x%d, no collectives" % world
-    out["config"]["control_plane"] = shard.control_plane()          # what carried the barriers / the MAX of the wall times
-    if is_gpu and devices_used != reported:
-        out["devices_used"] = devices_used
-    if sustained is not None:
-        out["sustained"] = sustained
-    if rank == 0 and world == 1 and not args.no_companions and hasattr(work, "companions"):
-        out.update(work.companions(sync))
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        out.update(work.host_side_checks())
-    elif rank == 0:
-        out["cpu_baseline"] = None
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        import torch.distributed as dist
-        dist.destroy_process_group()
-    return out if rank == 0 else None
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ CPU side (rank 0, N = 1)
@@ -587,13 +635,54 @@ class HipWorkload:
     def metric_name(self):
         return "sim steps/sec at batch=%dx%d contacts, %s" % (self.B, self.nc, "fwd" if self.args.fwd_only else "fwd+bwd")
 
+    def outputs(self):
+        """What the timed path hands its caller, from the buffers every step writes (after the timed region: its last step's results):
+        new velocities and poses (contact-list step) or the solution x, z, s, y (dense boundary), iteration counts and status words, and
+        the backward's gradients - the seven dense ones (grad_Q .. grad_F) or those w.r.t. the physical inputs (--bwd physical)."""
+        a = self.args
+        if a.mode == "dense":
+            s = self.sol
+            out = {"x": s.x, "z": s.z, "s": s.s, "y": s.y, "iters": s.iters, "status": s.status}
+        else:
+            out = {k: self.step_out.get(k) for k in ("v_new", "p_new", "iters", "status")}
+        if not a.fwd_only:
+            if a.bwd == "physical":
+                out.update({"grad_" + k: v for k, v in self.pgrads.items()})
+            else:
+                out.update({"grad_" + k: t for k, t in zip("QpGhAbF", self.grads) if t is not None})
+        return out
+
+    def config(self, world):
+        """The workload this run timed, its launch form, spin-up and the solver's iteration counts / status words of the last step."""
+        a, B, nc, nz, m, e = self.args, self.B, self.nc, self.nz, self.m, self.e
+        iters = (self.sol.iters if a.mode == "dense" else self.step_out["iters"]).double()
+        st = (self.sol.status if a.mode == "dense" else self.step_out["status"]).cpu()
+        # which BASELINE.json config the flags amount to (the default run is configs[2], the one the metric is quoted on)
+        cfg = {(1024, 8): "configs[1]", (4096, 16): "configs[2]", (32768, 16): "configs[3] on one GPU", (4096, 64): "configs[4]"}.get(
+            (B, nc), "configs[3]" if (B * world, nc) == (32768, 16) else "variant")
+        what = "forward only" if a.fwd_only else "forward + backward (implicit diff)"
+        shape = ("ten-box pile (4-3-2-1 pyramid), %d pts/interface" % a.pts) if self.pile else "%d-box stack, %d pts/interface" % (a.nbox, a.pts)
+        return {"workload": "%s: batch=%d x %d contacts (%s; nz %d, nineq %d, "
+                            "neq %d) per GPU, fp32 I/O, LCP %s, mode=%s, bwd=%s%s"
+                            % (cfg, B, nc, shape, nz, m, e, what, a.mode, "none" if a.fwd_only else a.bwd,
+                               "; step outputs: new_v and the moved pose (engines.py:76-77, bodies.py:80-82), multipliers kept in the "
+                               "workspace in fp64" if a.mode == "fused" else ""),
+                "launch": ("one HIP graph replay per step (forward + backward captured once)" if self.graph is not None
+                           else "eager: one ctypes call per kernel launch"),
+                "device_spin_up_s": round(self.spinup_s, 3), "device_spin_up_steps": self.spinup_steps,
+                "mean_pdipm_iters": float(iters.mean()), "nonzero_status": int((st != 0).sum()),
+                "status_bits": {name: int(((st & bit) != 0).sum()) for name, bit in
+                                (("singular_Q", 1), ("singular_S11", 2), ("singular_T", 4), ("nan", 8), ("truncated", 16))}}
+
     def report(self, samples, world):
+        """{"config": ...} and, given the event-timed kernel samples (--full), the "roofline" object."""
+        if samples is None:
+            return {"config": self.config(world)}
         from lcp_physics_amd import flops
         a, B, nb, nc, nz, m, e = self.args, self.B, self.nb, self.nc, self.nz, self.m, self.e
         fwd_ms = sum(s[0] for s in samples) / len(samples)
         bwd_ms = sum(s[1] for s in samples) / len(samples)
         iters = (self.sol.iters if a.mode == "dense" else self.step_out["iters"]).double()
-        status = (self.sol.status if a.mode == "dense" else self.step_out["status"])
         it_list = iters.cpu().tolist()
         fl_alg = float(sum(flops.flops_forward(nz, m, e, it) for it in it_list))
         # the contact-list entry points run the body-space variant of lcp_fwd_quad (nz <= 16, fp64 arithmetic; the stack scenes pin
@@ -621,11 +710,6 @@ class HipWorkload:
                      "lcp_fwd_solo_9_3_8" if (body_space and B <= 1024 and (nz, e, nc) == (9, 3, 8)) else
                      "lcp_fwd_quad_f64_fused_two_waves" if (sized and B > 4096) else
                      "lcp_fwd_quad_%s_%s" % ("f64" if a.compute == "f64" else "f32", a.mode))   # (the variant this mode runs)
-        # which BASELINE.json config the flags amount to (the default run is configs[2], the one the metric is quoted on)
-        cfg = {(1024, 8): "configs[1]", (4096, 16): "configs[2]", (32768, 16): "configs[3] on one GPU", (4096, 64): "configs[4]"}.get(
-            (B, nc), "configs[3]" if (B * world, nc) == (32768, 16) else "variant")
-        what = "forward only" if a.fwd_only else "forward + backward (implicit diff)"
-        st = status.cpu()
         tf = lambda fl, ms: fl / (ms * 1e-3) / 1e12
         if dense_pile and not primal:
             kname = ("lcp_classify_big + lcp_big_kernel<64, false, DENSE> (LCP_PATH_CONTACT_SPACE: the reference's T of pdipm.py:414-454 reduced to "
@@ -752,21 +836,7 @@ class HipWorkload:
             if btj:
                 roof["bwd"]["traffic_source"] = btj["source"]
                 roof["bwd"]["counters_stale"] = bool(btj.get("counters_stale"))
-        shape = ("ten-box pile (4-3-2-1 pyramid), %d pts/interface" % a.pts) if self.pile else "%d-box stack, %d pts/interface" % (a.nbox, a.pts)
-        return {
-            "config": {"workload": "%s: batch=%d x %d contacts (%s; nz %d, nineq %d, "
-                                   "neq %d) per GPU, fp32 I/O, LCP %s, mode=%s, bwd=%s%s"
-                                   % (cfg, B, nc, shape, nz, m, e, what, a.mode, "none" if a.fwd_only else a.bwd,
-                                      "; step outputs: new_v and the moved pose (engines.py:76-77, bodies.py:80-82), multipliers kept in the "
-                                      "workspace in fp64" if a.mode == "fused" else ""),
-                       "launch": ("one HIP graph replay per step (forward + backward captured once)" if self.graph is not None
-                                  else "eager: one ctypes call per kernel launch"),
-                       "device_spin_up_s": round(self.spinup_s, 3), "device_spin_up_steps": self.spinup_steps,
-                       "mean_pdipm_iters": float(iters.mean()), "nonzero_status": int((st != 0).sum()),
-                       "status_bits": {name: int(((st & bit) != 0).sum()) for name, bit in
-                                       (("singular_Q", 1), ("singular_S11", 2), ("singular_T", 4), ("nan", 8), ("truncated", 16))}},
-            "roofline": roof,
-        }
+        return {"config": self.config(world), "roofline": roof}
 
     def host_side_checks(self):
         """cpu_baseline, cpu_reference and the parity object (512 scenes sampled over the batch)."""

@@ -45,7 +45,8 @@ def _json_line(stdout):
     return json.loads(lines[0])
 
 
-SMALL = ["--steps", "3", "--warmup", "1", "--batch", "256", "--no-cpu-baseline", "--sustain", "0"]
+# (--full: these tests read the per-rank records and the roofline, which a plain run does not measure)
+SMALL = ["--steps", "3", "--warmup", "1", "--batch", "256", "--no-cpu-baseline", "--sustain", "0", "--full"]
 
 
 def test_bench_gpus_flag_launches_that_many_ranks_or_refuses():
@@ -87,3 +88,44 @@ def test_bench_single_rank_line_has_the_contract_fields():
     assert rf["flops"] == "executed" and 0 < rf["frac"] < 1.0 and rf["frac"] < rf["frac_algorithmic"]
     assert rf["bwd"]["bound"] == "hbm" and 0 < rf["bwd"]["frac"] < 1.0
     assert [r["rank"] for r in j["per_rank"]] == [0] and j["per_rank"][0]["fwd_ms"] > 0
+
+
+def test_bench_plain_line_and_dumped_outputs_are_the_timed_step():
+    """A plain run (no --full) prints the headline fields without the --full objects; --dump-outputs writes what the timed path returned
+    in its last step: bitwise the fused step and the dense backward of bench.py's scenes (seed 1236, cotangent seed 4321) computed
+    here, and identical across two runs with the same arguments."""
+    import tempfile
+
+    import numpy as np
+    from lcp_physics_amd import scenes
+    from lcp_physics_amd.lcp import lcp_backward
+    from lcp_physics_amd.physics import assemble_contacts, fused_step
+    from lcp_physics_amd.physics.batched_world import solution_of_step
+    plain = ["--steps", "3", "--warmup", "1", "--batch", "256"]
+    with tempfile.TemporaryDirectory() as tmp:
+        dumps = []
+        for k in range(2):
+            d = os.path.join(tmp, "run%d" % k)
+            r = _bench(plain + ["--dump-outputs", d])
+            assert r.returncode == 0, r.stderr[-2000:]
+            j = _json_line(r.stdout)
+            for f in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup"):
+                assert f in j, f
+            for f in ("roofline", "per_rank", "sustained", "cpu_baseline", "parity", "graph_ms_per_step", "general_kernel"):
+                assert f not in j, f
+            assert j["steps"] == 3 and j["n_gpus"] == 1 and j["ms_per_step"] > 0 and j["dtype"] == "f64"
+            assert abs(j["value"] - 256 / (j["ms_per_step"] * 1e-3)) < 1e-6 * j["value"]
+            dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))})
+    a, b = dumps
+    assert sorted(a) == sorted(b) == sorted(["v_new", "p_new", "iters", "status"] + ["grad_" + n for n in "QpGhAbF"])
+    assert all(a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], b[k]) for k in a)
+    sc = scenes.make_stack_scenes(B=256, nbox=4, pts_per_interface=4, seed=1236, dtype=torch.float32).to(device="cuda:0")
+    cot = torch.randn(256, 15, generator=torch.Generator().manual_seed(4321), dtype=torch.float32).to("cuda:0")
+    lcp = assemble_contacts(sc)
+    out = fused_step(sc, multipliers=False)
+    grads = lcp_backward(solution_of_step(sc, out, lcp[2], lcp[4]), cot)
+    torch.cuda.synchronize()
+    assert np.array_equal(a["v_new"], out["v_new"].cpu().numpy()) and np.array_equal(a["p_new"], out["p_new"].cpu().numpy())
+    assert np.array_equal(a["iters"], out["iters"].double().cpu().numpy())
+    for n, g in zip("QpGhAbF", grads):
+        assert np.array_equal(a["grad_" + n], g.cpu().numpy()), n

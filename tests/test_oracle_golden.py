@@ -1,9 +1,11 @@
 """CPU: pin the clean-room oracle against the reference.
 
 * against the committed fixtures (outputs of the unmodified reference recorded by
-  oracle/make_golden.py) - runs everywhere;
-* live against /root/reference when it is present (marker `reference`).
+  oracle/make_golden.py and oracle/make_golden_engine_scenes.py) - runs everywhere.
 """
+import os
+
+import numpy as np
 import pytest
 import torch
 
@@ -127,20 +129,20 @@ def test_backward_equals_finite_differences_for_symmetric_F():
         assert torch.allclose(fd, gr["dp"][:, j], rtol=1e-4, atol=1e-6)
 
 
-@pytest.mark.reference
 def test_oracle_matches_live_reference_on_random_engine_scenes():
-    """Live: run the unmodified reference per scene (batch 1) on synthetic stack scenes
-    and compare the vectorised per-scene oracle."""
-    from oracle import ref_shim
-    mods = ref_shim.load_reference()
+    """The unmodified reference run per scene (batch 1) on synthetic stack scenes - its answers recorded in
+    tests/golden/engine_scenes.npz by oracle/make_golden_engine_scenes.py - against the vectorised per-scene oracle."""
     from lcp_physics_amd import scenes
-    sc = scenes.make_stack_scenes(B=6, nbox=2, pts_per_interface=2, seed=11, dtype=torch.float64)
+    d = np.load(os.path.join(golden_io.GOLDEN_DIR, "engine_scenes.npz"))
+    B, nbox, pts, seed = (int(v) for v in d["scenes"])
+    sc = scenes.make_stack_scenes(B=B, nbox=nbox, pts_per_interface=pts, seed=seed, dtype=torch.float64)
     Q, p, G, h, A, b, F = O.assemble_lcp(*sc.assembly_args())
+    for nm, t in zip("QpGhAbF", (Q, p, G, h, A, b, F)):          # the scenes the reference was given
+        assert torch.allclose(t, torch.from_numpy(d["in_" + nm]), rtol=1e-12, atol=1e-12), nm
+    x_ref, lams, slacks = (torch.from_numpy(d[k]) for k in ("x", "lams", "slacks"))
     sol = O.lcp_forward(Q, p, G, h, A, b, F)
     for i in range(Q.shape[0]):
-        fn = mods["engines"].LCPFunction(max_iter=10, verbose=-1)
-        x = fn(Q[i:i + 1], p[i:i + 1], G[i:i + 1], h[i:i + 1], A[i:i + 1], b[i:i + 1], F[i:i + 1])
-        ex = parity.err_x(sol.x[i:i + 1], x, Q[i:i + 1], p[i:i + 1])
+        ex = parity.err_x(sol.x[i:i + 1], x_ref[i:i + 1], Q[i:i + 1], p[i:i + 1])
         assert float(ex) < 1e-9
         assert torch.equal(parity.active_sets(sol.z[i:i + 1], sol.s[i:i + 1]),
-                           parity.active_sets(fn.lams, fn.slacks))
+                           parity.active_sets(lams[i:i + 1], slacks[i:i + 1]))

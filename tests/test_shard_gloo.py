@@ -100,12 +100,13 @@ class _NoLaunchWork:
         return {}
 
 
-def _bench_worker(rank, world, port, q):
+def _bench_worker(rank, world, port, q, full=True):
     os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world),
                       MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     sys.path.insert(0, ROOT)
     import bench
-    args = bench.parse(["--gpus", str(world), "--steps", "5", "--warmup", "2", "--batch", "4096", "--sustain", "0"])
+    args = bench.parse(["--gpus", str(world), "--steps", "5", "--warmup", "2", "--batch", "4096", "--sustain", "0"]
+                       + (["--full"] if full else []))
     out = bench.run_rank(args, _NoLaunchWork, device="cpu")
     if rank == 0:
         q.put(out)
@@ -141,6 +142,62 @@ def test_bench_rank_protocol_gloo_ranks(world):
     assert all(r["host_us_per_step"] >= 20e3 * (r["rank"] + 1) for r in pr)
     assert out["host_us_per_step"] == max(r["host_us_per_step"] for r in pr)
     assert abs(out["host_bound_ceiling"]["value"] - 4096 * world / (out["host_us_per_step"] * 1e-6)) < 1e-6 * out["host_bound_ceiling"]["value"]
+
+
+def test_bench_plain_run_times_the_steps_and_nothing_else():
+    """Without --full the rank protocol runs the warm-up and timed steps only (no host-issue probe, no kernel samples, no sustained
+    loop, no CPU-side checks) and the line carries the headline fields and the workload's description."""
+    world = 2
+    ctx = mp.get_context("spawn")
+    q = ctx.SimpleQueue()
+    port = _free_port()
+    procs = [ctx.Process(target=_bench_worker, args=(r, world, port, q, False)) for r in range(world)]
+    for p in procs:
+        p.start()
+    for p in procs:
+        p.join(180)
+        assert p.exitcode == 0
+    out = q.get()
+    assert out["config"]["calls"] == 7                      # warm-up + timed steps: nothing else called step()
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup"):
+        assert k in out, k
+    for k in ("per_rank", "host_us_per_step", "host_bound_ceiling", "sustained", "cpu_baseline", "parity"):
+        assert k not in out, k
+    assert out.get("roofline") is None                      # (the stand-in's report has no roofline either way)
+    assert out["n_gpus"] == world and out["steps"] == 5 and out["ms_per_step"] >= 20.0 * world
+    assert abs(out["value"] - 4096 * world * 5 / (out["ms_per_step"] * 5e-3)) < 1e-6 * out["value"]
+
+
+def test_dump_outputs_writes_float_arrays_and_a_fixed_sample_within_the_budget(tmp_path, monkeypatch):
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    B = 1000
+    g = torch.Generator().manual_seed(3)
+    outs = {"v_new": torch.randn(B, 5, 3, generator=g), "grad_F": torch.randn(B, 16, 16, generator=g),
+            "iters": torch.randint(0, 11, (B,), dtype=torch.int32, generator=g), "x64": torch.randn(B, 9, generator=g, dtype=torch.float64),
+            "y": None}
+    # everything fits: all scenes, float32 kept, the rest as float64, None skipped
+    names = bench.dump_outputs(outs, str(tmp_path / "all"))
+    assert names == ["grad_F", "iters", "v_new", "x64"]
+    for k in names:
+        a = np.load(tmp_path / "all" / (k + ".npy"))
+        assert a.dtype == (np.float32 if outs[k].dtype == torch.float32 else np.float64)
+        assert np.array_equal(a, outs[k].double().numpy() if a.dtype == np.float64 else outs[k].numpy())
+    # over the budget: the same seeded sample of scenes in every file, in ascending order, the same from call to call
+    budget = 200 << 10
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", budget)
+    bench.dump_outputs(outs, str(tmp_path / "s1"))
+    bench.dump_outputs(outs, str(tmp_path / "s2"))
+    files = sorted(os.listdir(tmp_path / "s1"))
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in files) <= budget
+    a1 = {f: np.load(tmp_path / "s1" / f) for f in files}
+    assert all(np.array_equal(a1[f], np.load(tmp_path / "s2" / f)) for f in files)
+    n = a1["iters.npy"].shape[0]
+    assert 0 < n < B and all(a.shape[0] == n for a in a1.values())
+    rows = [int(np.nonzero((outs["x64"].numpy() == r).all(1))[0][0]) for r in a1["x64.npy"]]
+    assert rows == sorted(rows) and len(set(rows)) == n
+    assert np.array_equal(a1["v_new.npy"], outs["v_new"][rows].numpy())
 
 
 def _run_bench(argv, env_extra=None, timeout=300):

@@ -1,10 +1,10 @@
 #!/bin/bash
 # A/B: run bench.py against every library variant under lcp_physics_amd/csrc/variants/
-mkdir -p gpurun_out
+O=${OUT:-bench_out}; mkdir -p $O
 for lib in lcp_physics_amd/csrc/variants/*.so; do
   n=$(basename $lib .so)
-  LCP_HIP_LIB=$PWD/$lib timeout 200 python bench.py --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline ${EXTRA} > gpurun_out/ab_$n.json 2> gpurun_out/ab_$n.err
-  python - "$n" gpurun_out/ab_$n.json <<'PY'
+  LCP_HIP_LIB=$PWD/$lib timeout 200 python bench.py --full --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline ${EXTRA} > $O/ab_$n.json 2> $O/ab_$n.err
+  python - "$n" $O/ab_$n.json <<'PY'
 import json, sys
 try:
     d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])

@@ -10,22 +10,22 @@ mkdir -p $O
 cd $ROOT
 # PROFILES_ONLY=1: skip the bench / world / experiment lines and collect only the rocprofv3 traces, PMC passes and phase profiles
 run() { [ -n "$PROFILES_ONLY" ] && return 0; name=$1; shift; timeout 300 "$@" > $O/${TAG}_$name.json 2> $O/${TAG}_$name.err; tail -1 $O/${TAG}_$name.json | cut -c1-160; }
-run bench_fused python bench.py
-run bench_driver_form python bench.py --steps 20 --warmup 5
-run bench_dense python bench.py --mode dense --cpu-budget 3
-run bench_dense_contact_space python bench.py --mode dense --contact-space --cpu-budget 3
-run bench_fused_physical_bwd python bench.py --bwd physical --no-cpu-baseline
-run bench_config2_fwd_only python bench.py --config 1 --no-cpu-baseline
-run bench_config4_on_1gpu python bench.py --batch 32768 --no-cpu-baseline
-run bench_fused_8contacts python bench.py --pts 2 --no-cpu-baseline
-run bench_config5 python bench.py --config 4
-run bench_config1_parity python bench.py --config 1
-run bench_config2_parity python bench.py --config 2
-run bench_config3_parity python bench.py --config 3
-run bench_config4_parity python bench.py --config 4 --no-cpu-baseline
-run bench_config5_dense python bench.py --config 4 --mode dense --cpu-budget 5
-run bench_config5_dense_contact_space python bench.py --config 4 --mode dense --contact-space --no-cpu-baseline
-run bench_2ranks_one_device python bench.py --gpus 2 --share-devices --steps 20 --warmup 5 --no-cpu-baseline
+run bench_fused python bench.py --full
+run bench_driver_form python bench.py --full --steps 20 --warmup 5
+run bench_dense python bench.py --full --mode dense --cpu-budget 3
+run bench_dense_contact_space python bench.py --full --mode dense --contact-space --cpu-budget 3
+run bench_fused_physical_bwd python bench.py --full --bwd physical --no-cpu-baseline
+run bench_config2_fwd_only python bench.py --full --config 1 --no-cpu-baseline
+run bench_config4_on_1gpu python bench.py --full --batch 32768 --no-cpu-baseline
+run bench_fused_8contacts python bench.py --full --pts 2 --no-cpu-baseline
+run bench_config5 python bench.py --full --config 4
+run bench_config1_parity python bench.py --full --config 1
+run bench_config2_parity python bench.py --full --config 2
+run bench_config3_parity python bench.py --full --config 3
+run bench_config4_parity python bench.py --full --config 4 --no-cpu-baseline
+run bench_config5_dense python bench.py --full --config 4 --mode dense --cpu-budget 5
+run bench_config5_dense_contact_space python bench.py --full --config 4 --mode dense --contact-space --no-cpu-baseline
+run bench_2ranks_one_device python bench.py --full --gpus 2 --share-devices --steps 20 --warmup 5 --no-cpu-baseline
 # BENCH_ONLY=1: just the bench.py lines above (e.g. after tools/make_profile_json.py has refreshed the JSONs they quote)
 [ -n "$BENCH_ONLY" ] && exit 0
 run bench_midsize_24 python tools/bench_midsize.py 6 4
@@ -38,8 +38,8 @@ run bench_world_6bodies python tools/bench_world.py --nbox 5 --box 40 --cpu-scen
 # (round 6) 20 bodies: the generic kernels forward, and RECORDED roll-outs with their backward under torch's sync-debug-mode "error"
 run bench_world_20bodies python tools/bench_world.py --batch 1024 --nbox 19 --maxc 48 --steps 20 --settle 10 --record 4 --cpu-scenes 1
 run bench_world_20bodies_post_stab python tools/bench_world.py --batch 1024 --nbox 19 --maxc 48 --steps 20 --settle 10 --record 4 --cpu-scenes 0 --post-stab
-run bench_step_20bodies_physical python bench.py --nbox 19 --pts 2 --batch 1024 --bwd physical --no-cpu-baseline
-[ -n "$PROFILES_ONLY" ] || timeout 900 python bench.py --gpus 8 --share-devices --no-cpu-baseline > $O/${TAG}_bench_8ranks_one_device.json 2> $O/${TAG}_bench_8ranks_one_device.err
+run bench_step_20bodies_physical python bench.py --full --nbox 19 --pts 2 --batch 1024 --bwd physical --no-cpu-baseline
+[ -n "$PROFILES_ONLY" ] || timeout 900 python bench.py --full --gpus 8 --share-devices --no-cpu-baseline > $O/${TAG}_bench_8ranks_one_device.json 2> $O/${TAG}_bench_8ranks_one_device.err
 run batch_curve_2box python tools/bench_batch_curve.py 2
 run batch_curve_4box python tools/bench_batch_curve.py 4
 run engine_latency python tools/experiments/engine_latency.py
@@ -56,7 +56,7 @@ bash tools/profile_config5.sh $TAG > $O/${TAG}_profile_config5.log 2>&1
 cd /tmp && export TMPDIR=/tmp
 for v in "dense5:" "dense5cs:--contact-space"; do
   tag=${v%%:*}; extra=${v#*:}
-  BENCH="python $ROOT/bench.py --config 4 --mode dense $extra --steps 10 --warmup 2 --no-cpu-baseline --no-companions --spinup 0 --event-samples 8"
+  BENCH="python $ROOT/bench.py --full --config 4 --mode dense $extra --steps 10 --warmup 2 --no-cpu-baseline --no-companions --spinup 0 --event-samples 8"
   timeout 300 rocprofv3 --kernel-trace --stats -d $O/prof_${TAG}_${tag}_trace -o trace -- $BENCH > $O/prof_${TAG}_${tag}_trace.log 2>&1
   for ctr in FETCH_SIZE WRITE_SIZE "SQ_WAVES SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_VALU_MFMA_BUSY_CYCLES"; do
     name=$(echo $ctr | tr ' ' '_' | cut -c1-24)

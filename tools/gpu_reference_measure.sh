@@ -24,5 +24,5 @@ timeout 600 python oracle/time_reference.py --batch 1024 --dtype float32 --reps 
 timeout 600 python oracle/time_reference.py --batch 128 --dtype float64 --reps 1 --pile --machine "$M" > $O/${TAG}_reference_cpu_timing_pile.jsonl 2>/dev/null; cut -c1-20,180-330 $O/${TAG}_reference_cpu_timing_pile.jsonl
 fi
 # the bench line WITH the reference timed inside the run (cpu_reference.measured_in_this_run = true)
-timeout 600 python bench.py > $O/${TAG}_bench_fused_with_reference.json 2> $O/${TAG}_bench_fused_with_reference.err; python -c "
+timeout 600 python bench.py --full > $O/${TAG}_bench_fused_with_reference.json 2> $O/${TAG}_bench_fused_with_reference.err; python -c "
 import json; j = json.loads(open('$O/${TAG}_bench_fused_with_reference.json').read().strip().splitlines()[-1]); print(j['value'], j['cpu_reference'])"
