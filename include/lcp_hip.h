@@ -312,11 +312,12 @@ int lcp_post_stabilization_has_backward(int nb, int maxc, int e, int compute);
  * Geometry and poses are fp64 (tol = 1e-6 against coordinates of several hundred cannot be resolved in
  * fp32); the contact frame handed to the LCP kernels is fp32.
  *   in : kind[B,nb] (0 circle, 1 hull)  radius[B,nb]  verts_local[B,nb,8,2] (body frame, CCW as the
- *        reference's Hull.verts)  nverts[B,nb]  p_start[B,nb,3] (rot,x,y)  v[B,nb,3] (NULL: detect at p_start)
+ *        reference's Hull.verts; lcp_move_find_contacts_nv_f64 takes other capacities)  nverts[B,nb]  p_start[B,nb,3]
+ *        (rot,x,y)  v[B,nb,3] (NULL: detect at p_start)
  *   out: p_out[B,nb,3]  c_n/c_p1/c_p2[B,maxc,2]  c_pen[B,maxc]  c_i1/c_i2[B,maxc]  count[B] (contacts found,
  *        in the reference's order; > maxc means the list was truncated)  max_pen[B]  dt_used[B]
  *        t[B] (+= dt_used)  trials[B]   (c_pen, max_pen, dt_used, t, trials, p_out may be NULL)
- * nb <= 32, hulls of <= 8 vertices. */
+ * nb <= 32, hulls of <= 8 vertices (LCP_E_TOOLARGE beyond; larger scenes: lcp_move_find_contacts_nv_f64). */
 int lcp_move_find_contacts_f64(int B, int nb, int maxc,
                                const int32_t* kind, const double* radius, const double* verts_local,
                                const int32_t* nverts, const uint8_t* no_contact,
@@ -371,13 +372,45 @@ int lcp_state_update_backward_f64(int B, int nb, int nj,
  * SAT), hull / hull (SAT, incident edge, clipping); the derivative follows the branches the detection took (as autograd does).
  *   in : the geometry and the pose `p` lcp_move_find_contacts_f64 detected the contact list at (its p_out), its `eps`,
  *        count[B], and g_n / g_p1 / g_p2 [B,maxc,2] = d(loss)/d(c_n, c_p1, c_p2) (what lcp_step_backward_f32 returns)
- *   out: dp[B,nb,3] = d(loss)/d(pose) through the contact frame (overwritten).   nb <= 32. */
+ *   out: dp[B,nb,3] = d(loss)/d(pose) through the contact frame (overwritten).   nb <= 32, hulls of <= 8 vertices
+ *   (LCP_E_TOOLARGE beyond; larger scenes: lcp_contact_frame_backward_nv_f64). */
 int lcp_contact_frame_backward_f64(int B, int nb, int maxc,
                                    const int32_t* kind, const double* radius, const double* verts_local,
                                    const int32_t* nverts, const uint8_t* no_contact,
                                    const double* p, double eps, const int32_t* count,
                                    const float* g_n, const float* g_p1, const float* g_p2,
                                    double* dp, void* stream);
+
+/* lcp_move_find_contacts_f64 for hulls of up to 64 vertices and scenes of up to 64 bodies (the reference's Hull takes any
+ * number of vertices, bodies.py:154-250; World.find_contacts any number of bodies, world.py:139-142).  Same arguments, same
+ * semantics and outputs (pair order i < j, no_contact, count > maxc reported, padding, p_out / max_pen / dt_used / t / trials), plus
+ *   nvcap            the vertex capacity of verts_local[B,nb,nvcap,2], 8 <= nvcap <= 64 (hulls of 3 .. nvcap vertices)
+ *   scene_verts_max  an upper bound of sum(nverts) over the hulls of any one scene, <= 1024 (it sizes the LDS: 60 B per vertex)
+ * LCP_E_TOOLARGE for nb > 64, nvcap outside [8, 64] or scene_verts_max > 1024 (checked before any launch); a scene whose
+ * vertices exceed scene_verts_max gets count = -1 and no records.  Same double-precision geometry in the same order as
+ * lcp_move_find_contacts_f64: on the sizes both take, the outputs are bitwise the same (lcp_contacts_wide.hip). */
+int lcp_move_find_contacts_nv_f64(int B, int nb, int maxc, int nvcap, int scene_verts_max,
+                                  const int32_t* kind, const double* radius, const double* verts_local,
+                                  const int32_t* nverts, const uint8_t* no_contact,
+                                  const double* p_start, const float* v,
+                                  double dt, double dt_floor, int strict, int max_trials,
+                                  double eps, double tol,
+                                  double* p_out, float* c_n, float* c_p1, float* c_p2, double* c_pen,
+                                  int32_t* c_i1, int32_t* c_i2, int32_t* count, double* max_pen,
+                                  double* dt_used, double* t, int32_t* trials, void* stream);
+
+/* lcp_contact_frame_backward_f64 at the sizes of lcp_move_find_contacts_nv_f64 (nb <= 64, verts_local[B,nb,nvcap,2] with
+ * 8 <= nvcap <= 64, scene_verts_max <= 1024), plus the records' body indices c_i1 / c_i2 [B,maxc] of that detection: the
+ * work is one lane per (contacting pair, pose coordinate) over the first min(count, maxc) records, summed per coordinate in
+ * record order (deterministic).  no_contact is accepted for symmetry and not read (a masked pair has no records).
+ * LCP_E_TOOLARGE beyond those sizes or when the LDS (40 B per vertex + 52 B per contact slot) exceeds 152 KB. */
+int lcp_contact_frame_backward_nv_f64(int B, int nb, int maxc, int nvcap, int scene_verts_max,
+                                      const int32_t* kind, const double* radius, const double* verts_local,
+                                      const int32_t* nverts, const uint8_t* no_contact,
+                                      const double* p, double eps, const int32_t* count,
+                                      const int32_t* c_i1, const int32_t* c_i2,
+                                      const float* g_n, const float* g_p1, const float* g_p2,
+                                      double* dp, void* stream);
 
 /* ---- debugging / A-B aids (not part of the drop-in surface) ----
  * lcp_debug_set_trace: when non-NULL, the dense forward writes trace[B, max_iter, 4] =

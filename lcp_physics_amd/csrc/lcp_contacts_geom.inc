@@ -3,6 +3,9 @@
 // LCP_S = Dual (value + one directional derivative: the forward-mode derivative of the contact frame with respect to a
 // pose coordinate, for lcp_contact_frame_backward_f64).  Branches are taken on the VALUES, so the derivative is the one
 // autograd gives the reference: along the branch the forward pass took.
+// A body's vertex / normal / edge-length arrays are read through the types VRef and SRef: plain pointers unless the includer
+// defines LCP_GEOM_VREF / LCP_GEOM_SREF (types with operator[](int) returning V2 / LCP_S; lcp_contacts_wide.hip forms the dual
+// vertices of its frame backward on read from staged values that way).
 struct V2 { LCP_S x, y; };
 __device__ __forceinline__ V2 v2(LCP_S x, LCP_S y) { V2 r; r.x = x; r.y = y; return r; }
 __device__ __forceinline__ V2 operator+(V2 a, V2 b) { return v2(a.x + b.x, a.y + b.y); }
@@ -14,20 +17,31 @@ __device__ __forceinline__ LCP_S dot(V2 a, V2 b) { return a.x * b.x + a.y * b.y;
 __device__ __forceinline__ LCP_S norm(V2 a) { return sqrt(a.x * a.x + a.y * a.y); }
 __device__ __forceinline__ V2 left_orth(V2 v) { return v2(v.y, -v.x); }              // utils.py:99-102
 
+#ifdef LCP_GEOM_VREF
+typedef LCP_GEOM_VREF VRef;
+#else
+typedef const V2* VRef;
+#endif
+#ifdef LCP_GEOM_SREF
+typedef LCP_GEOM_SREF SRef;
+#else
+typedef const LCP_S* SRef;
+#endif
+
 struct Body {             // world frame
   int kind;               // 0 circle, 1 hull
   V2 pos;
   LCP_S rad;
   int nv;
-  const V2* verts;        // hull vertices relative to pos, rotated (LDS)
-  const V2* nrm;          // outward unit normal of edge k = (verts[k], verts[k+1])  (LDS, formed once per trial pose)
-  const LCP_S* elen;     // length of edge k
+  VRef verts;             // hull vertices relative to pos, rotated (LDS)
+  VRef nrm;               // outward unit normal of edge k = (verts[k], verts[k+1])  (LDS, formed once per trial pose)
+  SRef elen;              // length of edge k
 };
 
 struct Pt { V2 n, p1, p2; LCP_S pen; };
 
 // contacts.py:207-217 (`>=`: last maximiser wins)
-__device__ __forceinline__ int support(const V2* pts, int n, V2 dir) {
+__device__ __forceinline__ int support(VRef pts, int n, V2 dir) {
   int best = -1; LCP_S bn = -1.0;
   for (int i = 0; i < n; ++i) { const LCP_S c = dot(pts[i], dir); if (c >= bn) { bn = c; best = i; } }
   return best;
@@ -88,7 +102,7 @@ __device__ __forceinline__ V2 closest(V2 p, const Simplex& sx, Simplex& keep) {
 
 // contacts.py:80-141: `circ` plays b1, `hull` b2
 __device__ __forceinline__ int circle_hull(const Body& circ, const Body& hull, double eps, bool circle_is_g2, Pt& out0) {
-  const V2* verts = hull.verts;
+  const VRef verts = hull.verts;
   const int nv = hull.nv;
   const V2 tp = circ.pos - hull.pos;
   Simplex sx, keep;

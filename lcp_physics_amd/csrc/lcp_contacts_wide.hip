@@ -1,0 +1,412 @@
+// lcp_contacts_wide.hip - the narrow phase of lcp_contacts.hip for hulls of up to 64 vertices and scenes of up to 64 bodies.
+//
+// Same job, same semantics, same geometry code (lcp_contacts_geom.inc) as lcp_move_find_contacts_kernel and
+// lcp_contact_frame_backward_kernel (see lcp_contacts.hip for the map to the reference); what differs is the staging:
+//   * the vertices of a scene are ONE packed list in LDS (body b owns [off[b], off[b] + nverts[b]), off = prefix sum of the
+//     nverts), sized at launch from the batch's largest per-scene vertex total - the reference's Hull takes any number of
+//     vertices (bodies.py:154-250) and World.find_contacts any number of bodies (world.py:139-142);
+//   * the geometry is included in a namespace of its own whose NV is 64, so the GJK iteration cap (4 NV) covers the largest
+//     hull (the reference loops `while True`, contacts.py:88);
+//   * the frame backward runs one lane per (contacting pair, pose coordinate) instead of one thread per scene, and forms the
+//     dual vertices / normals on read from the values staged once (d/d(rot) of R(rot) v is the 90-degree turn of the value;
+//     edge lengths do not depend on the pose).
+// Limits (checked on the host before a launch, lcp_api.cpp): nb <= 64, 8 <= nvcap <= 64 (verts_local[B,nb,nvcap,2]),
+// hulls of 3..nvcap vertices, at most 1024 vertices per scene.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "lcp_kernels.h"
+
+namespace lcp {
+namespace ctw {
+
+constexpr int NV = 64;          // max vertices of a hull (GJK iteration cap of the geometry code: 4 NV)
+constexpr int MAXB = 64;        // max bodies per scene (one lane per body in the offset scan)
+constexpr int FB_T = 256;       // threads per workgroup (one scene) of the frame backward
+
+#define LCP_S double
+#include "lcp_contacts_geom.inc"
+#undef LCP_S
+
+// ---- forward-mode derivative (value + one directional derivative), as in lcp_contacts.hip ------------------------------
+namespace ad {
+struct Dual {
+  double v, d;
+  __device__ __forceinline__ Dual() {}
+  __device__ __forceinline__ Dual(double a) : v(a), d(0.0) {}
+  __device__ __forceinline__ Dual(double a, double b) : v(a), d(b) {}
+};
+__device__ __forceinline__ Dual operator+(Dual a, Dual b) { return Dual(a.v + b.v, a.d + b.d); }
+__device__ __forceinline__ Dual operator-(Dual a, Dual b) { return Dual(a.v - b.v, a.d - b.d); }
+__device__ __forceinline__ Dual operator-(Dual a) { return Dual(-a.v, -a.d); }
+__device__ __forceinline__ Dual operator*(Dual a, Dual b) { return Dual(a.v * b.v, a.d * b.v + a.v * b.d); }
+__device__ __forceinline__ Dual operator/(Dual a, Dual b) { const double q = a.v / b.v; return Dual(q, (a.d - q * b.d) / b.v); }
+__device__ __forceinline__ Dual sqrt(Dual a) { const double r = ::sqrt(a.v); return Dual(r, 0.5 * a.d / r); }
+__device__ __forceinline__ bool operator<(Dual a, Dual b) { return a.v < b.v; }
+__device__ __forceinline__ bool operator<=(Dual a, Dual b) { return a.v <= b.v; }
+__device__ __forceinline__ bool operator>(Dual a, Dual b) { return a.v > b.v; }
+__device__ __forceinline__ bool operator>=(Dual a, Dual b) { return a.v >= b.v; }
+__device__ __forceinline__ bool operator==(Dual a, Dual b) { return a.v == b.v; }
+
+// A rotated vertex (or edge normal) u = R(rot) u_local of a body whose rotation carries the seed dr (1 or 0): the value from
+// LDS, the derivative d u / d rot * dr = dr (-u.y, u.x).  Translation seeds do not reach it (vertices are relative to pos).
+template <class V>
+struct TurnRef {
+  const double2* val;
+  double dr;
+  __device__ __forceinline__ V operator[](int k) const {
+    const double2 u = val[k];
+    V r; r.x = Dual(u.x, -u.y * dr); r.y = Dual(u.y, u.x * dr);
+    return r;
+  }
+};
+// an edge length: invariant under the pose
+struct ConstRef {
+  const double* val;
+  __device__ __forceinline__ Dual operator[](int k) const { return Dual(val[k]); }
+};
+#define LCP_S Dual
+#define LCP_GEOM_VREF TurnRef<V2>
+#define LCP_GEOM_SREF ConstRef
+#include "lcp_contacts_geom.inc"
+#undef LCP_GEOM_SREF
+#undef LCP_GEOM_VREF
+#undef LCP_S
+}  // namespace ad
+
+// Per-scene body table in LDS (static) and the packed vertex offsets: lane b of the (first) wave scans nverts.  A hull
+// contributes min(max(nverts, 0), nvcap) vertices, a circle none.  Returns the scene's vertex total (all lanes).
+__device__ __forceinline__ int stage_bodies(int scene, int nb, int nvcap, const int32_t* kind, const int32_t* nverts,
+                                            const double* radius, int* s_kind, int* s_off, double* s_rad) {
+  const int lane = threadIdx.x & 63;
+  int nvb = 0;
+  if (lane < nb) {
+    const int k = kind[(size_t)scene * nb + lane];
+    int n = nverts[(size_t)scene * nb + lane];
+    n = n < 0 ? 0 : (n > nvcap ? nvcap : n);
+    nvb = k != 0 ? n : 0;
+    if (threadIdx.x < 64) { s_kind[lane] = k; s_rad[lane] = radius[(size_t)scene * nb + lane]; }
+  }
+  int incl = nvb;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
+  if (threadIdx.x < 64 && lane < nb) { s_off[lane + 1] = incl; if (lane == 0) s_off[0] = 0; }
+  return __shfl(incl, 63, 64);
+}
+
+// ---------------------------------------------------------------- detection: World.step_dt's move / detect / halve loop
+// One wavefront per scene, lane = body pair (i < j, lexicographic), the up to 2016 pairs walked 64 at a time; the contacts are
+// compacted in pair order with a wave prefix sum.  Dynamic LDS: 4 arrays over the scene's packed vertex list (V = the host's
+// scene_verts_max): local and rotated vertices, edge normals (V2) and edge lengths, and the owning body of each vertex.
+__global__ void __launch_bounds__(64) lcp_move_find_contacts_wide_kernel(ContactArgs P, int nvcap, int vmax) {
+  extern __shared__ double2 s_dyn[];
+  V2* s_vloc = reinterpret_cast<V2*>(s_dyn);
+  V2* s_verts = s_vloc + vmax;
+  V2* s_nrm = s_verts + vmax;
+  double* s_elen = reinterpret_cast<double*>(s_nrm + vmax);
+  int* s_vbody = reinterpret_cast<int*>(s_elen + vmax);
+  __shared__ double s_pose[MAXB * 3];
+  __shared__ V2 s_sc[MAXB];
+  __shared__ double s_rad[MAXB];
+  __shared__ int s_kind[MAXB], s_off[MAXB + 1];
+  const int ll = threadIdx.x;
+  const int scene = blockIdx.x;
+  const int nb = P.nb;
+  const int npairs = nb * (nb - 1) / 2;
+  const int vtot = stage_bodies(scene, nb, nvcap, P.kind, P.nverts, P.radius, s_kind, s_off, s_rad);
+  if (vtot > vmax) {                                      // the caller's scene_verts_max is too small: no detection, count = -1
+    for (int slot = ll; slot < P.maxc; slot += 64) {
+      const size_t o = (size_t)scene * P.maxc + slot;
+      P.c_n[o * 2] = 0; P.c_n[o * 2 + 1] = 0; P.c_p1[o * 2] = 0; P.c_p1[o * 2 + 1] = 0; P.c_p2[o * 2] = 0; P.c_p2[o * 2 + 1] = 0;
+      if (P.c_pen) P.c_pen[o] = 0;
+      P.c_i1[o] = 0; P.c_i2[o] = 0;
+    }
+    if (ll == 0) P.count[scene] = -1;
+    return;
+  }
+  __syncthreads();
+  // geometry does not change over the trials: stage it in LDS once
+  for (int b = 0; b < nb; ++b) {
+    const int o = s_off[b], n = s_off[b + 1] - o;
+    const double* vl = P.verts_local + ((size_t)scene * nb + b) * nvcap * 2;
+    for (int k = ll; k < n; k += 64) { s_vloc[o + k] = v2(vl[2 * k], vl[2 * k + 1]); s_vbody[o + k] = b; }
+  }
+  double dt = P.dt;
+  int base = 0, trial = 0;
+  double maxpen = -1e300;
+  bool done = false;
+  for (;;) {
+    // bodies.py:80-82 (p <- p_start + v dt) and the vertex rotation of bodies.py:211-214
+    for (int idx = ll; idx < nb * 3; idx += 64) {
+      double pv = P.p_start[(size_t)scene * nb * 3 + idx];
+      if (P.v) pv += (double)P.v[(size_t)scene * nb * 3 + idx] * dt;
+      s_pose[idx] = pv;
+    }
+    __syncthreads();
+    for (int b = ll; b < nb; b += 64) { const double rot = s_pose[b * 3]; s_sc[b] = v2(sin(rot), cos(rot)); }
+    __syncthreads();
+    for (int idx = ll; idx < vtot; idx += 64) {
+      const int bdy = s_vbody[idx];
+      const double sn = s_sc[bdy].x, cs = s_sc[bdy].y;
+      const double lx = s_vloc[idx].x, ly = s_vloc[idx].y;
+      s_verts[idx] = v2(cs * lx - sn * ly, sn * lx + cs * ly);                      // utils.py:105-112
+    }
+    __syncthreads();
+    // edge normals and lengths of every hull, once per trial pose
+    for (int idx = ll; idx < vtot; idx += 64) {
+      const int bdy = s_vbody[idx], o = s_off[bdy], nvb = s_off[bdy + 1] - o, k = idx - o;
+      const V2 edge = s_verts[o + (k + 1) % nvb] - s_verts[idx];
+      const double en = norm(edge);
+      s_elen[idx] = en;
+      s_nrm[idx] = left_orth(edge) * (1.0 / en);
+    }
+    __syncthreads();
+    base = 0; maxpen = -1e300;
+    for (int p0 = 0; p0 < npairs; p0 += 64) {
+      const int pr = p0 + ll;
+      int cnt = 0, bi = 0, bj = 1;
+      Pt pt0, pt1;
+      pt0.n = v2(0, 0); pt0.p1 = pt0.n; pt0.p2 = pt0.n; pt0.pen = 0; pt1 = pt0;
+      if (pr < npairs) {
+        int rem = pr;                                           // pair index -> (i, j), i < j, lexicographic
+        while (rem >= nb - 1 - bi) { rem -= nb - 1 - bi; ++bi; }
+        bj = bi + 1 + rem;
+        const bool skip = P.no_contact && P.no_contact[((size_t)scene * nb + bi) * nb + bj];
+        if (!skip) {
+          Body b1, b2;
+          b1.kind = s_kind[bi]; b2.kind = s_kind[bj];
+          b1.pos = v2(s_pose[bi * 3 + 1], s_pose[bi * 3 + 2]); b2.pos = v2(s_pose[bj * 3 + 1], s_pose[bj * 3 + 2]);
+          b1.rad = s_rad[bi]; b2.rad = s_rad[bj];
+          const int o1 = s_off[bi], o2 = s_off[bj];
+          b1.nv = s_off[bi + 1] - o1; b2.nv = s_off[bj + 1] - o2;
+          b1.verts = s_verts + o1; b2.verts = s_verts + o2;
+          b1.nrm = s_nrm + o1; b2.nrm = s_nrm + o2; b1.elen = s_elen + o1; b2.elen = s_elen + o2;
+          cnt = collide_pair(b1, b2, P.eps, pt0, pt1);
+        }
+      }
+      // exclusive prefix sum of cnt over the wave (pair order = the reference's contact order)
+      int incl = cnt;
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) { const int o = __shfl_up(incl, off, 64); if (ll >= off) incl += o; }
+      const int excl = incl - cnt;
+      const int total = __shfl(incl, 63, 64);
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const Pt& pt = q == 0 ? pt0 : pt1;
+        const int slot = base + excl + q;
+        if (q < cnt && slot < P.maxc) {
+          const size_t o = (size_t)scene * P.maxc + slot;
+          P.c_n[o * 2] = (float)pt.n.x; P.c_n[o * 2 + 1] = (float)pt.n.y;
+          P.c_p1[o * 2] = (float)pt.p1.x; P.c_p1[o * 2 + 1] = (float)pt.p1.y;
+          P.c_p2[o * 2] = (float)pt.p2.x; P.c_p2[o * 2 + 1] = (float)pt.p2.y;
+          if (P.c_pen) P.c_pen[o] = pt.pen;
+          P.c_i1[o] = bi; P.c_i2[o] = bj;
+        }
+        if (q < cnt) maxpen = pt.pen > maxpen ? pt.pen : maxpen;
+      }
+      base += total;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { const double o = __shfl_xor(maxpen, off, 64); maxpen = o > maxpen ? o : maxpen; }
+    ++trial;
+    // world.py:95-101
+    const bool ok = !(base > 0 && maxpen > P.tol);
+    if (ok || (!P.strict && dt < P.dt_floor) || trial >= P.max_trials || !P.v) done = true;   // (max_trials: the reference would spin)
+    else dt *= 0.5;
+    if (__all(done)) break;
+    __syncthreads();
+  }
+  // pad the unused contact slots with a harmless record (no normal, bodies 0/0)
+  const int nfill = base < P.maxc ? base : P.maxc;
+  for (int slot = nfill + ll; slot < P.maxc; slot += 64) {
+    const size_t o = (size_t)scene * P.maxc + slot;
+    P.c_n[o * 2] = 0; P.c_n[o * 2 + 1] = 0; P.c_p1[o * 2] = 0; P.c_p1[o * 2 + 1] = 0; P.c_p2[o * 2] = 0; P.c_p2[o * 2 + 1] = 0;
+    if (P.c_pen) P.c_pen[o] = 0;
+    P.c_i1[o] = 0; P.c_i2[o] = 0;
+  }
+  if (P.p_out) for (int idx = ll; idx < nb * 3; idx += 64) P.p_out[(size_t)scene * nb * 3 + idx] = s_pose[idx];
+  if (ll == 0) {
+    P.count[scene] = base;                                  // may exceed maxc: the caller checks
+    if (P.max_pen) P.max_pen[scene] = base > 0 ? maxpen : 0.0;
+    if (P.dt_used) P.dt_used[scene] = dt;
+    if (P.t) P.t[scene] += dt;                              // world.py:122
+    if (P.trials) P.trials[scene] = trial;
+  }
+}
+
+// ---------------------------------------------------------------- backward of the contact frame
+// d(loss)/d(pose_b,q) = sum over the records of g_n . dn/d(pose_b,q) + g_p1 . dp1/d(..) + g_p2 . dp2/d(..)   (lcp_contacts.hip)
+// One workgroup per scene.  The work units are the distinct pairs among the first min(count, maxc) records (a pair's records
+// are consecutive in the list); lane w = (unit w / 6, pose coordinate w % 6 of the pair: rot, x, y of body i1, then of i2)
+// re-runs collide_pair on dual numbers with that seed and keeps its term in LDS; the terms are then summed per pose
+// coordinate in record order (the existing kernel's order; no atomics, so the result does not depend on timing).
+// Dynamic LDS: rotated vertices, edge normals (V2) and edge lengths of the packed vertex list (vmax), then per unit
+// (maxc): its six terms, its first record and its two bodies.
+__global__ void __launch_bounds__(FB_T) lcp_contact_frame_backward_wide_kernel(int nb, int maxc, int nvcap, int vmax, const int32_t* kind,
+                                                                             const double* radius, const double* verts_local,
+                                                                             const int32_t* nverts, const double* p, double eps,
+                                                                             const int32_t* count, const int32_t* c_i1,
+                                                                             const int32_t* c_i2, const float* g_n,
+                                                                             const float* g_p1, const float* g_p2, double* dp) {
+  extern __shared__ double2 s_dyn[];
+  double2* s_verts = s_dyn;
+  double2* s_nrm = s_verts + vmax;
+  double* s_elen = reinterpret_cast<double*>(s_nrm + vmax);
+  double* s_term = s_elen + vmax;                                     // [maxc][6]
+  int* s_ustart = reinterpret_cast<int*>(s_term + (size_t)maxc * 6); // [maxc + 1]
+  int* s_ub1 = s_ustart + maxc + 1;                                   // [maxc]
+  int* s_ub2 = s_ub1 + maxc;                                          // [maxc]
+  __shared__ double s_pose[MAXB * 3];
+  __shared__ double s_rad[MAXB];
+  __shared__ double2 s_sc[MAXB];
+  __shared__ int s_kind[MAXB], s_off[MAXB + 1];
+  __shared__ int s_nunits;
+  const int tid = threadIdx.x;
+  const int scene = blockIdx.x;
+  double* out = dp + (size_t)scene * nb * 3;
+  int ntot = count[scene];
+  ntot = ntot < 0 ? 0 : (ntot > maxc ? maxc : ntot);
+  const int vtot = stage_bodies(scene, nb, nvcap, kind, nverts, radius, s_kind, s_off, s_rad);   // (uniform over the workgroup)
+  if (vtot > vmax) {                                                  // scene_verts_max too small: no derivative
+    for (int i = tid; i < nb * 3; i += FB_T) out[i] = 0.0;
+    return;
+  }
+  for (int i = tid; i < nb * 3; i += FB_T) s_pose[i] = p[(size_t)scene * nb * 3 + i];
+  // the work units: wave 0 flags the records that start a pair and compacts their indices with a ballot
+  if (tid < 64) {
+    int nu = 0;
+    for (int r0 = 0; r0 < ntot; r0 += 64) {
+      const int r = r0 + tid;
+      int i1 = 0, i2 = 0;
+      bool start = false;
+      if (r < ntot) {
+        const size_t o = (size_t)scene * maxc + r;
+        i1 = c_i1[o]; i2 = c_i2[o];
+        start = r == 0 || i1 != c_i1[o - 1] || i2 != c_i2[o - 1];
+        i1 = i1 < 0 ? 0 : (i1 >= nb ? nb - 1 : i1); i2 = i2 < 0 ? 0 : (i2 >= nb ? nb - 1 : i2);   // (body indices stay in the table)
+      }
+      const uint64_t m = __ballot(start);
+      if (start) {
+        const int u = nu + __popcll(m & ((1ull << tid) - 1));
+        s_ustart[u] = r; s_ub1[u] = i1; s_ub2[u] = i2;
+      }
+      nu += __popcll(m);
+    }
+    if (tid == 0) { s_ustart[nu] = ntot; s_nunits = nu; }
+  }
+  __syncthreads();
+  for (int b = tid; b < nb; b += FB_T) { const double rot = s_pose[b * 3]; s_sc[b] = make_double2(sin(rot), cos(rot)); }
+  __syncthreads();
+  // rotated vertices (the detection kernel's arithmetic: the same values, hence the same branches)
+  for (int b = 0; b < nb; ++b) {
+    const int o = s_off[b], n = s_off[b + 1] - o;
+    const double* vl = verts_local + ((size_t)scene * nb + b) * nvcap * 2;
+    const double sn = s_sc[b].x, cs = s_sc[b].y;
+    for (int k = tid; k < n; k += FB_T) {
+      const double lx = vl[2 * k], ly = vl[2 * k + 1];
+      s_verts[o + k] = make_double2(cs * lx - sn * ly, sn * lx + cs * ly);          // utils.py:105-112
+    }
+  }
+  __syncthreads();
+  for (int b = 0; b < nb; ++b) {
+    const int o = s_off[b], n = s_off[b + 1] - o;
+    for (int k = tid; k < n; k += FB_T) {
+      const V2 a = v2(s_verts[o + k].x, s_verts[o + k].y);
+      const V2 c = v2(s_verts[o + (k + 1) % n].x, s_verts[o + (k + 1) % n].y);
+      const V2 edge = c - a;
+      const double en = norm(edge);
+      const V2 nr = left_orth(edge) * (1.0 / en);
+      s_elen[o + k] = en;
+      s_nrm[o + k] = make_double2(nr.x, nr.y);
+    }
+  }
+  __syncthreads();
+  const int nunits = s_nunits;
+  for (int w = tid; w < nunits * 6; w += FB_T) {
+    using ad::Dual;
+    const int u = w / 6, s = w - u * 6;
+    const int r0 = s_ustart[u], nrec = s_ustart[u + 1] - r0;
+    const int bi = s_ub1[u], bj = s_ub2[u];
+    ad::Body b[2];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int bb = q == 0 ? bi : bj;
+      const int seed = (s / 3 == q) ? s % 3 : -1;                   // 0 rot, 1 x, 2 y; -1: none
+      const int o = s_off[bb];
+      b[q].kind = s_kind[bb];
+      b[q].rad = Dual(s_rad[bb]);
+      b[q].nv = s_off[bb + 1] - o;
+      b[q].pos = ad::v2(Dual(s_pose[bb * 3 + 1], seed == 1 ? 1.0 : 0.0), Dual(s_pose[bb * 3 + 2], seed == 2 ? 1.0 : 0.0));
+      const double dr = seed == 0 ? 1.0 : 0.0;
+      b[q].verts.val = s_verts + o; b[q].verts.dr = dr;
+      b[q].nrm.val = s_nrm + o; b[q].nrm.dr = dr;
+      b[q].elen.val = s_elen + o;
+    }
+    ad::Pt pt0, pt1;
+    const int c2 = ad::collide_pair(b[0], b[1], eps, pt0, pt1);
+    double acc = 0.0;
+    for (int c = 0; c < c2 && c < nrec; ++c) {
+      const ad::Pt& pt = c == 0 ? pt0 : pt1;
+      const size_t o = ((size_t)scene * maxc + r0 + c) * 2;
+      acc += (double)g_n[o] * pt.n.x.d + (double)g_n[o + 1] * pt.n.y.d + (double)g_p1[o] * pt.p1.x.d + (double)g_p1[o + 1] * pt.p1.y.d
+           + (double)g_p2[o] * pt.p2.x.d + (double)g_p2[o + 1] * pt.p2.y.d;
+    }
+    s_term[w] = acc;
+  }
+  __syncthreads();
+  // per pose coordinate, the terms in record order
+  for (int i = tid; i < nb * 3; i += FB_T) {
+    const int bd = i / 3, c = i - bd * 3;
+    double sum = 0.0;
+    for (int u = 0; u < nunits; ++u) {
+      if (s_ub1[u] == bd) sum += s_term[u * 6 + c];
+      if (s_ub2[u] == bd) sum += s_term[u * 6 + 3 + c];
+    }
+    out[i] = sum;
+  }
+}
+
+static size_t detect_lds(int vmax) { return (size_t)vmax * (3 * sizeof(V2) + sizeof(double) + sizeof(int)); }
+static size_t frame_bwd_lds(int vmax, int maxc) {
+  return (size_t)vmax * (2 * sizeof(double2) + sizeof(double)) + (size_t)maxc * 6 * sizeof(double) + (size_t)(3 * maxc + 1) * sizeof(int);
+}
+constexpr size_t LDS_LIMIT = 160 * 1024 - 8 * 1024;    // (the static tables of the kernels take less than 8 KB)
+
+template <typename K>
+static int set_lds(K kernel, size_t bytes) {
+  if (bytes > 64 * 1024 &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
+    return LCP_E_LAUNCH;
+  return 0;
+}
+
+static bool wide_sizes_ok(int nb, int nvcap, int vmax) {
+  return nb >= 1 && nb <= MAXB && nvcap >= 8 && nvcap <= NV && vmax >= 0 && vmax <= CONTACTS_WIDE_MAX_SCENE_VERTS;
+}
+
+}  // namespace ctw
+
+int contacts_wide_launch(const ContactArgs& P, int nvcap, int scene_verts_max, void* stream) {
+  if (!ctw::wide_sizes_ok(P.nb, nvcap, scene_verts_max)) return LCP_E_TOOLARGE;
+  const int vmax = scene_verts_max < 1 ? 1 : scene_verts_max;
+  const size_t lds = ctw::detect_lds(vmax);
+  if (ctw::set_lds(ctw::lcp_move_find_contacts_wide_kernel, lds)) return LCP_E_LAUNCH;
+  hipLaunchKernelGGL(ctw::lcp_move_find_contacts_wide_kernel, dim3(P.B), dim3(64), lds, (hipStream_t)stream, P, nvcap, vmax);
+  return hipGetLastError() == hipSuccess ? 0 : LCP_E_LAUNCH;
+}
+
+int contact_frame_backward_wide_launch(int B, int nb, int maxc, int nvcap, int scene_verts_max, const int32_t* kind,
+                                       const double* radius, const double* verts_local, const int32_t* nverts, const double* p,
+                                       double eps, const int32_t* count, const int32_t* c_i1, const int32_t* c_i2,
+                                       const float* g_n, const float* g_p1, const float* g_p2, double* dp, void* stream) {
+  if (!ctw::wide_sizes_ok(nb, nvcap, scene_verts_max)) return LCP_E_TOOLARGE;
+  const int vmax = scene_verts_max < 1 ? 1 : scene_verts_max;
+  const size_t lds = ctw::frame_bwd_lds(vmax, maxc);
+  if (lds > ctw::LDS_LIMIT) return LCP_E_TOOLARGE;
+  if (ctw::set_lds(ctw::lcp_contact_frame_backward_wide_kernel, lds)) return LCP_E_LAUNCH;
+  hipLaunchKernelGGL(ctw::lcp_contact_frame_backward_wide_kernel, dim3(B), dim3(ctw::FB_T), lds, (hipStream_t)stream, nb, maxc, nvcap, vmax,
+                     kind, radius, verts_local, nverts, p, eps, count, c_i1, c_i2, g_n, g_p1, g_p2, dp);
+  return hipGetLastError() == hipSuccess ? 0 : LCP_E_LAUNCH;
+}
+
+}  // namespace lcp

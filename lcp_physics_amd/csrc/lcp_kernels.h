@@ -188,5 +188,13 @@ int contact_frame_backward_launch(int B, int nb, int maxc, const int32_t* kind, 
                                   const int32_t* nverts, const uint8_t* no_contact, const double* p, double eps,
                                   const int32_t* count, const float* g_n, const float* g_p1, const float* g_p2, double* dp,
                                   void* stream);
+// the same for hulls of up to 64 vertices (verts_local[B,nb,nvcap,2], 8 <= nvcap <= 64), up to 64 bodies and
+// CONTACTS_WIDE_MAX_SCENE_VERTS vertices per scene (packed per-scene vertex lists in LDS) - lcp_contacts_wide.hip
+constexpr int CONTACTS_WIDE_MAX_SCENE_VERTS = 1024;
+int contacts_wide_launch(const ContactArgs& P, int nvcap, int scene_verts_max, void* stream);
+int contact_frame_backward_wide_launch(int B, int nb, int maxc, int nvcap, int scene_verts_max, const int32_t* kind,
+                                       const double* radius, const double* verts_local, const int32_t* nverts, const double* p,
+                                       double eps, const int32_t* count, const int32_t* c_i1, const int32_t* c_i2,
+                                       const float* g_n, const float* g_p1, const float* g_p2, double* dp, void* stream);
 
 }  // namespace lcp

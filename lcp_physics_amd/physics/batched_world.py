@@ -617,8 +617,9 @@ class ContactWorld:
     Forces: a constant `f` or `force_fn(t)` (time-dependent, `forces.py:29-48`).  `step(differentiable=True)` records the
     step in torch's autograd graph (roll-out gradients, `demos/grad_demo.py`).  Joints: a constant Jacobian `Je`
     (Total/X/Y/Rot constraints) or a `JointSet` (revolute / fixed joints, Jacobian rebuilt every step and differentiated);
-    at most 32 bodies per scene.  Scenes with 3 nb <= 32, maxc <= 16, e <= 4 run on the four-scenes-per-wave solver, up to
-    64 contacts and 24 equality rows (3 nb + e <= 56) on the wave-per-scene body-space solver (both with a fused backward),
+    up to 64 bodies per scene and hulls of up to 64 vertices (`GeometryBatch.from_shapes(..., max_verts=...)`), 1024 hull
+    vertices per scene (beyond 32 bodies or 8 vertices per hull the detection runs on lcp_contacts_wide.hip).  Scenes with
+    3 nb <= 32, maxc <= 16, e <= 4 run on the four-scenes-per-wave solver, up to 64 contacts and 24 equality rows (3 nb + e <= 56) on the wave-per-scene body-space solver (both with a fused backward),
     anything else on the generic kernels; a differentiable step of such a size goes through the dense boundary
     (physics/dense_step.py: torch assembly on the device + `LCPFunction`, the reference's own route).
     `post_stab=True` (off by default, as in the reference: utils.py:30) adds the two launches of world.py:109-121 to a

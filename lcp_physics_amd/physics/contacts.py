@@ -7,6 +7,10 @@ Host-side mirror of the reference's contact pipeline for B independent scenes:
 The contact record has the reference's format `((normal, p1, p2, penetration), i1, i2)`
 (`contacts.py:203-204`), stored structure-of-arrays and padded to `maxc` contacts per scene with a
 per-scene `count`.  No CPU fallback.
+
+Sizes: hulls of up to 8 vertices in scenes of up to 32 bodies run on `lcp_move_find_contacts_f64` /
+`lcp_contact_frame_backward_f64` (lcp_contacts.hip); anything else, up to 64 vertices per hull (the capacity
+`verts_local.shape[2]`, 8..64), 64 bodies and 1024 hull vertices per scene, on the `_nv_` entries (lcp_contacts_wide.hip).
 """
 from dataclasses import dataclass
 
@@ -16,7 +20,9 @@ import torch
 from .. import _lib
 
 CIRCLE, HULL = 0, 1
-NV = 8                   # vertex capacity of a hull (lcp_contacts.hip)
+NV = 8                   # default vertex capacity of a hull (lcp_contacts.hip)
+NV_MAX = 64              # largest capacity / hull (lcp_contacts_wide.hip)
+NB_SMALL = 32            # bodies per scene of the lcp_contacts.hip entries
 EPSILON = 0.1            # physics/utils.py:16  (contact detection margin)
 TOL = 1e-6               # physics/utils.py:17  (allowed penetration)
 
@@ -25,14 +31,18 @@ TOL = 1e-6               # physics/utils.py:17  (allowed penetration)
 class GeometryBatch:
     """Collision geometry of the bodies of B scenes (constant over a simulation).
 
-    kind [B,nb] int32 (0 circle, 1 hull), radius [B,nb] f64, verts_local [B,nb,8,2] f64 (body frame, the
-    order of the reference's `Hull.verts`), nverts [B,nb] int32, no_contact [B,nb,nb] uint8 or None
-    (the pairs `World` excludes through `add_no_contact`, bodies.py:117-118)."""
+    kind [B,nb] int32 (0 circle, 1 hull), radius [B,nb] f64, verts_local [B,nb,cap,2] f64 (body frame, the
+    order of the reference's `Hull.verts`; cap = 8 by default, up to 64), nverts [B,nb] int32, no_contact [B,nb,nb]
+    uint8 or None (the pairs `World` excludes through `add_no_contact`, bodies.py:117-118).
+    scene_verts_max: the largest sum of hull vertices over one scene (a host int: it sizes the LDS of the wide kernels);
+    `from_shapes` sets it, otherwise it is computed on first use (one synchronisation) and cached - rebuild the batch
+    rather than editing `nverts` in place."""
     kind: torch.Tensor
     radius: torch.Tensor
     verts_local: torch.Tensor
     nverts: torch.Tensor
     no_contact: torch.Tensor = None
+    scene_verts_max: int = None
 
     @property
     def B(self):
@@ -42,33 +52,61 @@ class GeometryBatch:
     def nb(self):
         return self.kind.shape[1]
 
+    @property
+    def nvcap(self):
+        """Vertex capacity of a hull in `verts_local`."""
+        return self.verts_local.shape[2]
+
+    def verts_max(self):
+        """`scene_verts_max`, computed once (one device read) when it was not given."""
+        if self.scene_verts_max is None:
+            n = torch.where(self.kind != CIRCLE, self.nverts.clamp(0, self.nvcap), torch.zeros_like(self.nverts))
+            self.scene_verts_max = int(n.sum(dim=1).max()) if n.numel() else 0
+        return self.scene_verts_max
+
+    @property
+    def wide(self):
+        """True when the sizes need the lcp_contacts_wide.hip entries (capacity other than 8 or more than 32 bodies)."""
+        return self.nvcap != NV or self.nb > NB_SMALL
+
     def to(self, device):
         mv = lambda t: None if t is None else t.to(device).contiguous()
-        return GeometryBatch(mv(self.kind), mv(self.radius), mv(self.verts_local), mv(self.nverts), mv(self.no_contact))
+        return GeometryBatch(mv(self.kind), mv(self.radius), mv(self.verts_local), mv(self.nverts), mv(self.no_contact),
+                             self.scene_verts_max)
 
     @staticmethod
-    def from_shapes(shapes, B=1):
-        """`shapes`: per body ('circle', rad) or ('rect', (w, h)) or ('hull', verts[nv,2]); replicated B times."""
+    def from_shapes(shapes, B=1, max_verts=NV):
+        """`shapes`: per body ('circle', rad) or ('rect', (w, h)) or ('hull', verts[nv,2]); replicated B times.
+        `max_verts`: the vertex capacity of `verts_local` (8 .. 64; a larger hull raises ValueError); None: the largest hull's
+        vertex count, at least 8."""
         nb = len(shapes)
+        vlists = []
+        for k, a in shapes:
+            if k == "circle":
+                vlists.append(None)
+            elif k == "rect":                        # bodies.py:261-264: [half, half * (-1, 1), -half, -half * (-1, 1)]
+                hw, hh = float(a[0]) / 2, float(a[1]) / 2
+                vlists.append([[hw, hh], [-hw, hh], [-hw, -hh], [hw, -hh]])
+            else:
+                vlists.append(np.asarray(a, dtype=np.float64).tolist())
+        largest = max([len(v) for v in vlists if v is not None], default=0)
+        cap = max(NV, largest) if max_verts is None else int(max_verts)
+        if not NV <= cap <= NV_MAX:
+            raise ValueError("the vertex capacity must lie in [%d, %d] (got %d)" % (NV, NV_MAX, cap))
         kind = torch.zeros(nb, dtype=torch.int32)
         radius = torch.zeros(nb, dtype=torch.float64)
-        verts = torch.zeros(nb, NV, 2, dtype=torch.float64)
+        verts = torch.zeros(nb, cap, 2, dtype=torch.float64)
         nverts = torch.zeros(nb, dtype=torch.int32)
-        for i, (k, a) in enumerate(shapes):
+        for i, ((k, a), vs) in enumerate(zip(shapes, vlists)):
             if k == "circle":
                 kind[i], radius[i] = CIRCLE, float(a)
             else:
-                if k == "rect":                      # bodies.py:261-264: [half, half * (-1, 1), -half, -half * (-1, 1)]
-                    hw, hh = float(a[0]) / 2, float(a[1]) / 2
-                    vs = [[hw, hh], [-hw, hh], [-hw, -hh], [hw, -hh]]
-                else:
-                    vs = np.asarray(a, dtype=np.float64).tolist()
-                if len(vs) > NV:
-                    raise ValueError("hulls are limited to %d vertices" % NV)
+                if len(vs) > cap:
+                    raise ValueError("hulls are limited to %d vertices" % cap)
                 kind[i], nverts[i] = HULL, len(vs)
                 verts[i, :len(vs)] = torch.tensor(vs, dtype=torch.float64)
         rep = lambda t: t.unsqueeze(0).repeat(B, *([1] * t.dim())).contiguous()
-        return GeometryBatch(rep(kind), rep(radius), rep(verts), rep(nverts), None)
+        return GeometryBatch(rep(kind), rep(radius), rep(verts), rep(nverts), None, int(nverts.sum()))
 
 
 class ContactBuffers:
@@ -128,8 +166,9 @@ def move_and_find_contacts(geom, p_start, v, dt, maxc=16, eps=EPSILON, tol=TOL, 
     _lib.require_gpu_tensor(geom.radius, "radius", torch.float64)
     _lib.require_gpu_tensor(geom.verts_local, "verts_local", torch.float64)
     _lib.require_gpu_tensor(p_start, "p_start", torch.float64)
-    if tuple(p_start.shape) != (B, nb, 3) or tuple(geom.verts_local.shape) != (B, nb, NV, 2):
-        raise RuntimeError("p_start must be [B,nb,3] and verts_local [B,nb,%d,2]" % NV)
+    if (tuple(p_start.shape) != (B, nb, 3) or tuple(geom.verts_local.shape) != (B, nb, geom.nvcap, 2)
+            or not NV <= geom.nvcap <= NV_MAX):
+        raise RuntimeError("p_start must be [B,nb,3] and verts_local [B,nb,cap,2] with %d <= cap <= %d" % (NV, NV_MAX))
     if v is not None:
         _lib.require_gpu_tensor(v, "v", torch.float32)
     if geom.no_contact is not None:
@@ -140,13 +179,18 @@ def move_and_find_contacts(geom, p_start, v, dt, maxc=16, eps=EPSILON, tol=TOL, 
     if out is None:
         out = ContactBuffers(B, nb, maxc, dev)
     P = _lib.ptr
-    with torch.cuda.device(dev):
-        rc = lib.lcp_move_find_contacts_f64(
-            B, nb, out.maxc, P(geom.kind), P(geom.radius), P(geom.verts_local), P(geom.nverts), P(geom.no_contact),
+    args = (P(geom.kind), P(geom.radius), P(geom.verts_local), P(geom.nverts), P(geom.no_contact),
             P(p_start), P(v), float(dt), float(dt / 4 if dt_floor is None else dt_floor), int(bool(strict)),
             int(max_trials), float(eps), float(tol), P(out.p_out), P(out.c_n), P(out.c_p1), P(out.c_p2),
             P(out.c_pen), P(out.c_i1), P(out.c_i2), P(out.count), P(out.max_pen), P(out.dt_used), P(t),
             P(out.trials), _lib.stream_ptr(dev))
+    if geom.wide:
+        with torch.cuda.device(dev):
+            rc = lib.lcp_move_find_contacts_nv_f64(B, nb, out.maxc, geom.nvcap, geom.verts_max(), *args)
+        _lib.check(rc, "lcp_move_find_contacts_nv_f64")
+        return out
+    with torch.cuda.device(dev):
+        rc = lib.lcp_move_find_contacts_f64(B, nb, out.maxc, *args)
     _lib.check(rc, "lcp_move_find_contacts_f64")
     return out
 
@@ -159,7 +203,8 @@ def find_contacts(geom, p, maxc=16, eps=EPSILON, out=None):
 def contact_frame_backward(geom, p, cb, g_n, g_p1, g_p2, eps=EPSILON):
     """d(loss)/d(pose) through the contact frame (`lcp_contact_frame_backward_f64`): the chain rule of the reference's
     differentiable contact handler (`contacts.py:57-352`) for the contacts in `cb` detected at pose `p` [B,nb,3] float64 with
-    margin `eps` - every record type (circle / circle, circle / hull, hull / hull)."""
+    margin `eps` - every record type (circle / circle, circle / hull, hull / hull).  `cb`: the records (`ContactBuffers` or
+    a snapshot: c_n, c_i1, c_i2, count)."""
     lib = _lib.load()
     B, nb = geom.B, geom.nb
     dev = p.device
@@ -168,6 +213,14 @@ def contact_frame_backward(geom, p, cb, g_n, g_p1, g_p2, eps=EPSILON):
     _lib.require_gpu_tensor(p, "p", torch.float64)
     dp = torch.empty(B, nb, 3, dtype=torch.float64, device=dev)
     P = _lib.ptr
+    if geom.wide:
+        with torch.cuda.device(dev):
+            rc = lib.lcp_contact_frame_backward_nv_f64(B, nb, cb.c_n.shape[1], geom.nvcap, geom.verts_max(), P(geom.kind),
+                                                       P(geom.radius), P(geom.verts_local), P(geom.nverts), P(geom.no_contact),
+                                                       P(p), float(eps), P(cb.count), P(cb.c_i1), P(cb.c_i2), P(g_n), P(g_p1),
+                                                       P(g_p2), P(dp), _lib.stream_ptr(dev))
+        _lib.check(rc, "lcp_contact_frame_backward_nv_f64")
+        return dp
     with torch.cuda.device(dev):
         rc = lib.lcp_contact_frame_backward_f64(B, nb, cb.c_n.shape[1], P(geom.kind), P(geom.radius), P(geom.verts_local),
                                                 P(geom.nverts), P(geom.no_contact), P(p), float(eps), P(cb.count), P(g_n), P(g_p1),
