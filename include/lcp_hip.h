@@ -50,6 +50,10 @@ extern "C" {
  * a backward planned for another layout returns NaN gradients instead of misreading it. */
 #define LCP_PATH_CONTACT_SPACE 0x2000
 #define LCP_PATH_PRIMAL 0x4000
+/* Likewise: the contact-list step on one workgroup per scene in body space (lcp_primal_wg.hip) wherever its sizes allow - at most 128
+ * pivots (3 nb - 3 under LCP_HINT_PINNED with e = 3, else 3 nb + e with e <= 4), at most 256 contacts, fp64 arithmetic - also where
+ * another family would serve the call by default (A/B aid; the backward must carry the same bit). */
+#define LCP_PATH_PRIMAL_WG 0x80000
 /* Contact-list forwards of the four-scenes-per-wave sizes choose by batch size between four scenes per wavefront (lcp_quad.hip) and
  * one scene per wavefront (lcp_solo.hip, small batches); these force one of the two (A/B aids; same workspace layout, any backward
  * follows either). */
@@ -175,7 +179,8 @@ int lcp_assemble_contacts_f32(int B, int nb, int nc, int e,
  * lcp_pdipm_backward_f32 can follow (with G from lcp_assemble_contacts_f32).
  *   out: v_new[B,nb,3]  p_new[B,nb,3]  z[B,m]  s[B,m]  y[B,e]  iters[B]  status[B]
  *        z, s, y may be NULL: the multipliers are then not written out (the reference's step returns new_v only, engines.py:76-77;
- *        the backward reads them, in fp64, from the workspace either way). */
+ *        the backward reads them, in fp64, from the workspace either way).
+ * Sizes and kernel families as lcp_solve_dynamics_f32 (every scene at nc contacts). */
 int lcp_step_fused_f32(int B, int nb, int nc, int e,
                        const float* pos, const float* Mdiag, const float* v, const float* f,
                        const float* rest, const float* fric,
@@ -197,7 +202,9 @@ int lcp_step_fused_f32(int B, int nb, int nc, int e,
  * Sizes: 3 nb <= 16, nc <= 16, e <= 4 after either forward; 3 nb <= 32 with nc <= 16, and up to nc <= 64, 3 nb <= 43,
  * e <= 4 (fp64 arithmetic), after lcp_solve_dynamics_f32 only (its kernels own the workspace layout); 5 <= e <= 24 equality rows
  * (chains of joints) with nc <= 64 and 3 nb + e <= 56, or e <= 4 with 3 nb + e <= 64 (18 .. 20 bodies; round 6) (fp64 arithmetic) after either
- * forward; (round 6) every other size the generic
+ * forward; beyond those, up to 128 pivots (3 nb - 3 under LCP_HINT_PINNED with e = 3: 43 bodies; else 3 nb + e, e <= 4: 41 bodies)
+ * and up to 256 contacts (fp64 arithmetic) on the workgroup-per-scene body-space kernel (lcp_primal_wg.hip) after either forward;
+ * every other size the generic
  * kernels step forward - more than 64 contacts, 3 nb + e > 56, fp32 arithmetic beyond 16 contacts: lcp_step_bwd_kernel on the iterate
  * lcp_step_kernel leaves, each scene at its own contact count - after either forward, in either arithmetic.  LCP_E_TOOLARGE only for
  * the wave64 step family (fp32 arithmetic, 3 nb <= 16, 5 <= e <= 8: its kernel keeps no iterate) and beyond the generic plan. */
@@ -240,8 +247,11 @@ int lcp_step_backward_je_f32(int B, int nb, int nc, int e,
  * Larger scenes - maxc <= 64 with 3 nb + e <= 56 and e <= 24 (chains of joints: two rows per revolute joint), with 3 nb + e <= 64 and
  * e <= 4 (up to 20 bodies on a pinned floor: the 64-row instantiation, every lane of the wave a row; round 6), or 3 nb <= 43,
  * e <= 4 - run (fp64 arithmetic) on the wave-per-scene body-space kernel (BASELINE config 5) or the workgroup-per-scene
- * contact-space kernel, and can be followed by lcp_step_backward_f32 (not by the dense backward); anything else runs on the
- * generic kernels (LCP_E_TOOLARGE beyond their LDS / workspace plan), which keep each scene's iterate and its contact count for
+ * contact-space kernel, and can be followed by lcp_step_backward_f32 (not by the dense backward).  Beyond those, systems of up to 128
+ * pivots (3 nb - 3 under LCP_HINT_PINNED with e = 3: up to 43 bodies; 3 nb + e with e <= 4 otherwise: up to 41 bodies) with up to 256
+ * contacts run (fp64 arithmetic) on the workgroup-per-scene BODY-space kernel (lcp_primal_wg.hip: one workgroup of 256 threads per
+ * scene, the system in LDS), followed by lcp_step_backward_f32 as well (not by the dense backward); anything else - more pivots,
+ * 5 .. 24 equality rows beyond 56 rows, fp32 arithmetic - runs on the generic kernels (LCP_E_TOOLARGE beyond their LDS / workspace plan), which keep each scene's iterate and its contact count for
  * lcp_step_backward_f32 as well (round 6).
  *   out: v_new[B,nb,3]  z[B,4 maxc]  s[B,4 maxc]  y[B,e]  iters[B]  status[B] */
 int lcp_solve_dynamics_f32(int B, int nb, int maxc, int e, const int32_t* c_count,

@@ -23,6 +23,7 @@ PATH_QUAD = 0x8000
 PATH_SOLO = 0x10000
 HINT_PINNED = 0x20000
 BWD_ADJOINT = 0x40000
+PATH_PRIMAL_WG = 0x80000
 
 ST_SINGULAR_Q = 1
 ST_SINGULAR_S11 = 2
@@ -118,7 +119,8 @@ def require_gpu_tensor(t, name, dtype=None):
 
 
 _PATH_BITS = {"auto": 0, "wave64": 0, "generic": PATH_GENERIC, "big": PATH_CONTACT_SPACE, "primal": PATH_PRIMAL,
-              "quad": PATH_QUAD, "solo": PATH_SOLO}     # quad / solo: four scenes / one scene per wavefront at every batch size
+              "quad": PATH_QUAD, "solo": PATH_SOLO,      # quad / solo: four scenes / one scene per wavefront at every batch size
+              "primal_wg": PATH_PRIMAL_WG}              # one workgroup per scene in body space wherever its sizes allow
 _tls = threading.local()          # the default is per host thread, like the library's own debugging aids
 
 

@@ -16,15 +16,16 @@ thread_local double* g_trace = nullptr;   // debugging aid, see lcp_debug_set_tr
 thread_local int g_adjoint = 0;           // lcp_set_backward_adjoint: LCP_BWD_ADJOINT for the fp64-I/O backward (it has no `compute` word)
 thread_local int g_path = 0;              // this thread's DEFAULT kernel path for calls whose `compute` word names none:
                                           // 0 = automatic, 1 = generic kernels, 3 = contact-space kernels instead of the body-space ones,
-                                          // 4 = one wave per scene (lcp_primal.hip) at every size (A/B aids)
+                                          // 4 = one wave per scene (lcp_primal.hip) at every size, 5 = one workgroup per scene in body
+                                          // space (lcp_primal_wg.hip) wherever its sizes allow (A/B aids)
 
 constexpr int FLAG_BITS = LCP_BWD_ADJOINT | LCP_PATH_GENERIC | LCP_HINT_ALL_CONTACT | LCP_IO_F64 | LCP_PATH_CONTACT_SPACE | LCP_PATH_PRIMAL | LCP_PATH_QUAD | LCP_PATH_SOLO |
-                          LCP_HINT_PINNED;
+                          LCP_HINT_PINNED | LCP_PATH_PRIMAL_WG;
 
 // `compute` word of an entry point -> arithmetic type and kernel path.  The path is a function of the WORD whenever the word
 // names one (LCP_PATH_*): a forward and its backward that carry the same word pick the same kernel family on any two host
 // threads.  Only a word without path bits falls back on the calling thread's lcp_debug_set_path default.
-// *path: 0 automatic, 1 generic, 3 contact space, 4 primal;  *generic = (path == 1)
+// *path: 0 automatic, 1 generic, 3 contact space, 4 primal, 5 primal_wg;  *generic = (path == 1)
 inline int split_compute(int compute, bool* generic, int* path = nullptr, int* solo = nullptr) {
   // (same workspace layout either way: forward only; bit 2 of the value: LCP_HINT_PINNED)
   if (solo) *solo = ((compute & LCP_PATH_SOLO) ? 1 : ((compute & LCP_PATH_QUAD) ? 0 : -1)) + ((compute & LCP_HINT_PINNED) ? 16 : 0);
@@ -32,6 +33,7 @@ inline int split_compute(int compute, bool* generic, int* path = nullptr, int* s
   if (compute & LCP_PATH_GENERIC) p = 1;
   else if (compute & LCP_PATH_CONTACT_SPACE) p = 3;
   else if (compute & LCP_PATH_PRIMAL) p = 4;
+  else if (compute & LCP_PATH_PRIMAL_WG) p = 5;
   if (path) *path = p;
   *generic = p == 1;
   return compute & ~FLAG_BITS;
@@ -44,7 +46,8 @@ enum WsTag {
   TAG_DENSE_WAVE = 1, TAG_DENSE_BIG = 2, TAG_DENSE_GENERIC = 3,                       // lcp_pdipm_forward_*
   TAG_STEP_QUAD_BODY = 4, TAG_STEP_QUAD_CS = 5, TAG_STEP_PRIMAL = 6, TAG_STEP_BIG = 7, TAG_STEP_WAVE64 = 8, TAG_STEP_GENERIC = 9,
   TAG_POSTSTAB_PRIMAL = 10, TAG_POSTSTAB_GENERIC = 11,
-  TAG_DENSE_WAVE_BODY = 12                                                            // lcp_pdipm_forward_f32, class-2 scenes solved in body space (no W)
+  TAG_DENSE_WAVE_BODY = 12,                                                           // lcp_pdipm_forward_f32, class-2 scenes solved in body space (no W)
+  TAG_STEP_PRIMAL_WG = 13                                                             // contact-list step, one workgroup per scene in body space
 };
 constexpr size_t TRAILER_BYTES = 256;
 
@@ -57,13 +60,22 @@ inline bool use_wave64(int io_f64, int nz, int m, int e, bool generic) {
 
 // Kernel family of the contact-list entry points (lcp_step_fused_f32, lcp_solve_dynamics_f32, lcp_step_backward_f32):
 // ONE function of (sizes, arithmetic, forced path), so that a backward always reads the workspace layout its forward wrote.
-enum StepFamily { FAM_QUAD, FAM_PRIMAL, FAM_BIG, FAM_WAVE64, FAM_GENERIC };
-inline StepFamily step_family(int nz, int m, int e, int compute, int path) {
+enum StepFamily { FAM_QUAD, FAM_PRIMAL, FAM_BIG, FAM_PRIMAL_WG, FAM_WAVE64, FAM_GENERIC };
+inline size_t scene_bytes(int nz, int m, int e, int compute, int io_f64);
+// lcp_primal_wg.hip: its sizes, fp64 arithmetic, and its per-scene block within the stride the workspace already has there (so that
+// lcp_workspace_bytes stays what it was); automatic mode also only where the generic plan holds the size (no size gains or loses
+// LCP_E_TOOLARGE, lcp_step_has_backward answers as before)
+inline bool primal_wg_ok(int nz, int m, int e, int compute, bool pinned) {
+  return compute == LCP_COMPUTE_F64 && lcp::primal_wg_supported(nz, m, e, pinned) && lcp::primal_wg_ws_bytes(m) <= scene_bytes(nz, m, e, compute, 0);
+}
+inline StepFamily step_family(int nz, int m, int e, int compute, int path, bool pinned = false) {
   if (path == 1) return FAM_GENERIC;
   if (path == 4 && compute == LCP_COMPUTE_F64 && lcp::primal_supported(nz, m, e)) return FAM_PRIMAL;   // (A/B: one wave per scene at every size)
+  if (path == 5 && primal_wg_ok(nz, m, e, compute, pinned)) return FAM_PRIMAL_WG;   // (A/B: one workgroup per scene wherever it fits)
   if (lcp::quad_step_supported(nz, m, e)) return FAM_QUAD;                     // <= 16 contacts, <= 10 bodies, e <= 4
   if (compute == LCP_COMPUTE_F64 && path != 3 && lcp::primal_supported(nz, m, e)) return FAM_PRIMAL;   // <= 64 contacts, body-space systems
   if (compute == LCP_COMPUTE_F64 && lcp::big_supported(nz, m, e)) return FAM_BIG;   // <= 64 contacts (fp64 arithmetic)
+  if (path != 3 && primal_wg_ok(nz, m, e, compute, pinned) && lcp::make_plan(nz, m, e, 8).ok) return FAM_PRIMAL_WG;   // <= 128 pivots, <= 256 contacts
   if (lcp::wave64_supported(nz, m, e)) return FAM_WAVE64;                      // nz <= 16, e 5..8
   return FAM_GENERIC;
 }
@@ -82,6 +94,7 @@ inline int step_tag(StepFamily fam, int nz, int compute, int path) {
     case FAM_QUAD: return lcp::quad_step_is_body_space(nz, compute, path != 3) ? TAG_STEP_QUAD_BODY : TAG_STEP_QUAD_CS;
     case FAM_PRIMAL: return TAG_STEP_PRIMAL;
     case FAM_BIG: return TAG_STEP_BIG;
+    case FAM_PRIMAL_WG: return TAG_STEP_PRIMAL_WG;
     case FAM_WAVE64: return TAG_STEP_WAVE64;
     default: return TAG_STEP_GENERIC;
   }
@@ -231,7 +244,7 @@ static int backward_common(int io_f64, int B, int nz, int m, int e, const void* 
     // (in body space, no W in it: lcp_bwd_quad<..., BODY>, or in contact space, exactly as that forward decided), the wave64 step
     // kernel and the generic one (their dense layouts) -, the tag says which one it was.
     if (io_f64) return LCP_E_BADARG;
-    const StepFamily fam = step_family(nz, m, e, compute, path);
+    const StepFamily fam = step_family(nz, m, e, compute, path, pinned);
     P.tag_value = step_tag(fam, nz, compute, path);
     if (fam == FAM_QUAD) {
       if (!lcp::quad_supported(nz, m, e)) return LCP_E_TOOLARGE;             // (nz 17..32: the physical backward only)
@@ -248,7 +261,7 @@ static int backward_common(int io_f64, int B, int nz, int m, int e, const void* 
       P.tag_value = TAG_STEP_GENERIC; P.skip_tag = TAG_STEP_WAVE64;
       return lcp::generic_backward(P, io_f64, compute, pl.lds_bytes, stream);
     }
-    if (fam != FAM_GENERIC) return LCP_E_TOOLARGE;                            // (lcp_primal / lcp_big: lcp_step_backward_f32 is their backward)
+    if (fam != FAM_GENERIC) return LCP_E_TOOLARGE;                            // (lcp_primal / lcp_big / lcp_primal_wg: lcp_step_backward_f32 is their backward)
     return lcp::generic_backward(P, io_f64, compute, pl.lds_bytes, stream);
   }
   if (w64) return lcp::wave64_backward(P, compute, false, stream, io_f64, dense_body);
@@ -360,13 +373,14 @@ int lcp_step_backward_je_f32(int B, int nb, int nc, int e, const float* Mdiag, c
   G.dcn = dc_n; G.dcp1 = dc_p1; G.dcp2 = dc_p2; G.dJe = (e > 0) ? dJe : nullptr;
   // the same family decision as the forward entry points (launch_step): a function of the sizes and the `compute` word; the
   // kernels check the tag that forward left in the workspace trailer
-  const StepFamily fam = step_family(3 * nb, 4 * nc, e, compute, path);
+  const StepFamily fam = step_family(3 * nb, 4 * nc, e, compute, path, pinned);
   P.tag = trailer_of(ws, B, scene_bytes(3 * nb, 4 * nc, e, compute, 0));
   P.tag_value = step_tag(fam, 3 * nb, compute, path);
   switch (fam) {
     case FAM_QUAD: return lcp::quad_step_backward(P, G, compute, stream, path != 3, pinned);
     case FAM_PRIMAL: return lcp::primal_step_backward(P, G, stream, pinned);
     case FAM_BIG: return lcp::big_step_backward(P, G, stream);
+    case FAM_PRIMAL_WG: return lcp::primal_wg_step_backward(P, G, stream, pinned);
     case FAM_GENERIC: {                      // (round 6) any size the generic plan holds: lcp_step_bwd_kernel on the iterate lcp_step_kernel kept
       const int cs = (compute == LCP_COMPUTE_F64) ? 8 : 4;
       lcp::Plan pl = lcp::make_plan(3 * nb, 4 * nc, e, cs);
@@ -382,16 +396,17 @@ int lcp_step_has_backward(int nb, int maxc, int e, int compute) {
   if (nb <= 0 || maxc <= 0 || e < 0) return 0;
   bool generic;
   int path;
+  const bool pinned = (compute & LCP_HINT_PINNED) != 0;
   compute = split_compute(compute, &generic, &path);
   if (compute != LCP_COMPUTE_F32 && compute != LCP_COMPUTE_F64) return 0;
-  const StepFamily fam = step_family(3 * nb, 4 * maxc, e, compute, path);
+  const StepFamily fam = step_family(3 * nb, 4 * maxc, e, compute, path, pinned);
   if (fam == FAM_GENERIC) return lcp::make_plan(3 * nb, 4 * maxc, e, (compute == LCP_COMPUTE_F64) ? 8 : 4).ok ? 1 : 0;
-  return (fam == FAM_QUAD || fam == FAM_PRIMAL || fam == FAM_BIG) ? 1 : 0;
+  return (fam == FAM_QUAD || fam == FAM_PRIMAL || fam == FAM_BIG || fam == FAM_PRIMAL_WG) ? 1 : 0;
 }
 
 // forward of the contact-list entry points, by family
 static int launch_step(lcp::StepArgs& P, int nz, int m, int e, int compute, int path, void* stream, int solo) {
-  StepFamily fam = step_family(nz, m, e, compute, path);
+  StepFamily fam = step_family(nz, m, e, compute, path, solo >= 8);
   if (fam == FAM_WAVE64 && P.c_count) fam = FAM_GENERIC;                    // (its kernel takes full lists only)
   P.tag = trailer_of(P.ws, P.B, scene_bytes(nz, m, e, compute, 0));
   P.tag_value = step_tag(fam, nz, compute, path);
@@ -399,6 +414,7 @@ static int launch_step(lcp::StepArgs& P, int nz, int m, int e, int compute, int 
     case FAM_QUAD: return lcp::quad_step(P, compute, stream, path != 3, solo >= 8 ? solo - 16 : solo, solo >= 8);
     case FAM_PRIMAL: return lcp::primal_step(P, stream, solo >= 8);
     case FAM_BIG: return lcp::big_step(P, stream);
+    case FAM_PRIMAL_WG: return lcp::primal_wg_step(P, stream, solo >= 8);
     case FAM_WAVE64: return lcp::wave64_step(P, compute, stream);
     default: break;
   }

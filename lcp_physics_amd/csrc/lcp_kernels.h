@@ -148,6 +148,12 @@ int primal_post_stab(const StepArgs& P, void* stream);                          
 int primal_dense_forward(const FwdArgs& P, int32_t* cls, size_t ws_scene, void* stream);      // scenes of class 3 (and 4: the pinned form)
 int primal_dense_backward(const BwdArgs& P, int32_t* cls, size_t ws_scene, void* stream);
 
+// body-space contact-list step beyond one wavefront: one workgroup of 256 threads per scene, the fp64 system in LDS - lcp_primal_wg.hip
+bool primal_wg_supported(int nz, int m, int e, bool pinned);   // <= 128 pivots (pinned: nz - 3; otherwise nz + neq, neq <= 4), <= 256 contacts
+size_t primal_wg_ws_bytes(int m);                              // per scene: contact count, best iterate (x, y, z, s)
+int primal_wg_step(const StepArgs& P, void* stream, bool pinned = false);
+int primal_wg_step_backward(const StepArgs& P, const StepBwdArgs& G, void* stream, bool pinned = false);
+
 // four-scenes-per-wave contact-structured path (nc <= 16, neq <= 4, diagonal Q; nz <= 16, or nz <= 32 from a contact
 // list) - lcp_quad.hip
 // `accept`: classification flag value (workspace meta[0]) the launch serves

@@ -1,9 +1,12 @@
 """The wide narrow phase (lcp_contacts_wide.hip) on one GPU: detection and frame-backward launch times for B scenes of a floor and
 nb - 1 circles, rects and 16-gons settled into piles; the whole `ContactWorld.step()` and a recorded step + backward at that size;
 and the wide detection against lcp_contacts.hip on the 4-box BASELINE world (the same scenes, capacity 16 vs 8).
+The solve alone: lcp_solve_dynamics_f32 on the settled contact lists, forward and forward + lcp_step_backward_f32, on the kernel
+family `--path` picks (auto | generic | primal_wg; the piles always settle on the automatic path, so every path solves the same
+lists).  `--solve-only` skips the detection, world-step and BASELINE timings.
 Device-synchronised timing after a spin-up; prints one JSON line (stamped with the kernel sources' hash) and writes it to --out.
 
-    python tools/bench_wide_contacts.py [--batch 4096] [--nb 48] [--reps 20] [--out profiles/wide_contacts.json]
+    python tools/bench_wide_contacts.py [--batch 4096] [--nb 48] [--reps 20] [--path auto] [--solve-only] [--out profiles/wide_contacts.json]
 """
 import argparse, json, os, sys, time
 
@@ -73,9 +76,12 @@ def main():
     ap.add_argument("--settle", type=int, default=30, help="untimed steps before the timed region (the piles settle)")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--spinup", type=float, default=1.0, help="seconds of untimed launches first (device clocks settle)")
+    ap.add_argument("--path", default="auto", choices=["auto", "generic", "primal_wg"], help="kernel family of the timed solves")
+    ap.add_argument("--solve-only", action="store_true", help="time the solve alone (skip detection, world steps, BASELINE world)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    from lcp_physics_amd import scenes
+    from lcp_physics_amd import _lib, scenes
+    from lcp_physics_amd.physics import batched_world as bw
     from lcp_physics_amd.physics import contacts as ct
     from lcp_physics_amd.srchash import source_sha256
     dev = torch.device("cuda")
@@ -96,7 +102,34 @@ def main():
     gs = [torch.randn(B, args.maxc, 2, generator=gen).to(dev) for _ in range(3)]
     res = {"tool": "bench_wide_contacts", "batch": B, "nb": args.nb, "maxc": args.maxc, "settle_steps": args.settle,
            "scene_verts_max": geom.scene_verts_max, "nvcap": geom.nvcap, "contacts_mean": float(counts.mean()),
-           "contacts_max": int(counts.max()), "gpu": torch.cuda.get_device_name(0), "source_sha256": source_sha256()}
+           "contacts_max": int(counts.max()), "gpu": torch.cuda.get_device_name(0), "source_sha256": source_sha256(), "path": args.path}
+    # the solve alone on the settled lists (what ContactWorld.step launches after detection)
+    sc = world
+    e = 3
+    dl_dv = torch.randn(B, args.nb, 3, generator=gen).to(dev)
+    solve = lambda: bw.solve_dynamics(B, args.nb, args.maxc, e, cb.count, sc.Mdiag, sc.v, sc.f, sc.rest, sc.fric, cb, sc.Je, sc.dt,
+                                      path=args.path, pinned=sc._pinned)
+    out = solve()
+    torch.cuda.synchronize()
+    res["solve_tag"] = int(out["ws"][-256:-252].cpu().numpy().view(np.int32)[0]) if out["ws"].numel() == _lib.workspace_bytes(
+        B, 3 * args.nb, 4 * args.maxc, e, _lib.COMPUTE_F64) else None
+    res["solve_status_nan"] = int(((out["status"] & _lib.ST_NAN) != 0).sum())
+    sreps = max(3, args.reps // 4) if args.path == "generic" else args.reps
+
+    def solve_fwd_bwd():
+        o = solve()
+        bw.solve_dynamics_backward(B, args.nb, args.maxc, e, sc.Mdiag, sc.v, sc.f, sc.rest, sc.fric, cb, sc.Je, sc.dt, dl_dv, o)
+
+    solve_fwd_bwd()
+    res["solve_forward_ms"] = timed(solve, sreps)
+    res["solve_forward_backward_ms"] = timed(solve_fwd_bwd, sreps)
+    if args.solve_only:
+        line = json.dumps(res)
+        print(line)
+        if args.out:
+            with open(args.out, "w") as fh:
+                fh.write(line + "\n")
+        return
     res["detect_ms"] = timed(lambda: ct.find_contacts(geom, p, maxc=args.maxc, out=cb), args.reps)
     res["frame_backward_ms"] = timed(lambda: ct.contact_frame_backward(geom, p, cb, *gs), args.reps)
     res["world_step_ms"] = timed(world.step, args.reps)
