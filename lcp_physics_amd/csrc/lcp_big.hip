@@ -1272,31 +1272,17 @@ bool big_dense_supported(int nz, int m, int e) {
   return nz <= 64;
 }
 
-static void dense_io(DenseIO& DN, int nz, int m, int32_t* cls, size_t ws_scene) { DN = DenseIO{}; DN.nz = nz; DN.m = m; DN.cls = cls; DN.ws_scene = ws_scene; }
-
 int big_dense_forward(const FwdArgs& P, int32_t* cls, size_t ws_scene, int primal_ok, void* stream) {
-  DenseIO DN;
-  dense_io(DN, P.nz, P.m, cls, ws_scene);
-  DN.Q = (const float*)P.Q; DN.p = (const float*)P.p; DN.G = (const float*)P.G; DN.h = (const float*)P.h;
-  DN.A = (const float*)P.A; DN.b = (const float*)P.b; DN.F = (const float*)P.F;
+  const DenseIO DN = dense_io(P, cls, ws_scene);
   hipLaunchKernelGGL(big::lcp_classify_big, dim3(P.B), dim3(256), 0, (hipStream_t)stream, DN, P.e, primal_ok & 1, (primal_ok >> 1) & 1, (unsigned char*)P.ws);
-  StepArgs SP = {};
-  SP.B = P.B; SP.nb = (P.nz + 2) / 3; SP.nc = P.m / 4; SP.e = P.e; SP.ws = P.ws;
-  SP.eps = P.eps; SP.max_iter = P.max_iter; SP.lim = P.lim;
-  SP.v_new = P.x; SP.z = P.z; SP.s = P.s; SP.y = P.y; SP.iters = P.iters; SP.status = P.status;
-  SP.tag = P.tag; SP.tag_value = P.tag_value;
+  const StepArgs SP = dense_step_args(P, (P.nz + 2) / 3);
   StepBwdArgs Gd = {};
   return big_class(SP.nc) == 32 ? big_launch<32, false, true>(SP, Gd, stream, DN) : big_launch<64, false, true>(SP, Gd, stream, DN);
 }
 
 int big_dense_backward(const BwdArgs& P, int32_t* cls, size_t ws_scene, void* stream) {
-  DenseIO DN;
-  dense_io(DN, P.nz, P.m, cls, ws_scene);
-  DN.G = (const float*)P.G; DN.A = (const float*)P.A; DN.dl_dx = (const float*)P.dl_dx;
-  DN.dQ = (float*)P.dQ; DN.dp = (float*)P.dp; DN.dG = (float*)P.dG; DN.dh = (float*)P.dh; DN.dA = (float*)P.dA; DN.db = (float*)P.db; DN.dF = (float*)P.dF;
-  StepArgs SP = {};
-  SP.B = P.B; SP.nb = (P.nz + 2) / 3; SP.nc = P.m / 4; SP.e = P.e; SP.ws = P.ws;
-  SP.tag = (int32_t*)P.tag; SP.tag_value = P.tag_value;
+  const DenseIO DN = dense_io(P, cls, ws_scene);
+  const StepArgs SP = dense_step_args(P, (P.nz + 2) / 3);
   StepBwdArgs Gd = {};
   return big_class(SP.nc) == 32 ? big_launch<32, true, true>(SP, Gd, stream, DN) : big_launch<64, true, true>(SP, Gd, stream, DN);
 }

@@ -67,6 +67,20 @@ struct DenseIO {
   const float* dl_dx;                               // backward: cotangent, then the seven gradients (any may be NULL)
   float *dQ, *dp, *dG, *dh, *dA, *db, *dF;
 };
+inline DenseIO dense_io(const FwdArgs& P, int32_t* cls, size_t ws_scene) {
+  DenseIO DN = {};
+  DN.nz = P.nz; DN.m = P.m; DN.cls = cls; DN.ws_scene = ws_scene;
+  DN.Q = (const float*)P.Q; DN.p = (const float*)P.p; DN.G = (const float*)P.G; DN.h = (const float*)P.h;
+  DN.A = (const float*)P.A; DN.b = (const float*)P.b; DN.F = (const float*)P.F;
+  return DN;
+}
+inline DenseIO dense_io(const BwdArgs& P, int32_t* cls, size_t ws_scene) {
+  DenseIO DN = {};
+  DN.nz = P.nz; DN.m = P.m; DN.cls = cls; DN.ws_scene = ws_scene;
+  DN.G = (const float*)P.G; DN.A = (const float*)P.A; DN.dl_dx = (const float*)P.dl_dx;
+  DN.dQ = (float*)P.dQ; DN.dp = (float*)P.dp; DN.dG = (float*)P.dG; DN.dh = (float*)P.dh; DN.dA = (float*)P.dA; DN.db = (float*)P.db; DN.dF = (float*)P.dF;
+  return DN;
+}
 
 struct StepArgs {
   int B, nb, nc, e;
@@ -90,6 +104,22 @@ struct StepArgs {
   int32_t* tag;             // workspace trailer word (see FwdArgs::tag): written by the forward kernels, compared by the backward ones
   int tag_value;
 };
+// the contact-list arguments of a dense call on the contact-structured kernels (lcp_big.hip, lcp_primal.hip); `nb`: the bodies the
+// unit's kernels see in nz columns
+inline StepArgs dense_step_args(const FwdArgs& P, int nb) {
+  StepArgs SP = {};
+  SP.B = P.B; SP.nb = nb; SP.nc = P.m / 4; SP.e = P.e; SP.ws = P.ws;
+  SP.eps = P.eps; SP.max_iter = P.max_iter; SP.lim = P.lim;
+  SP.v_new = P.x; SP.z = P.z; SP.s = P.s; SP.y = P.y; SP.iters = P.iters; SP.status = P.status;
+  SP.tag = P.tag; SP.tag_value = P.tag_value;
+  return SP;
+}
+inline StepArgs dense_step_args(const BwdArgs& P, int nb) {
+  StepArgs SP = {};
+  SP.B = P.B; SP.nb = nb; SP.nc = P.m / 4; SP.e = P.e; SP.ws = P.ws;
+  SP.tag = (int32_t*)P.tag; SP.tag_value = P.tag_value;
+  return SP;
+}
 
 struct StepBwdArgs {
   const void* dl_dv;                                   // [B, nb, 3]  d(loss)/d(v_new)
@@ -132,10 +162,10 @@ int wave64_forward(const FwdArgs& P, int compute, void* stream, int io_f64 = 0, 
 int wave64_backward(const BwdArgs& P, int compute, bool all_quad, void* stream, int io_f64 = 0, int body_space = 0);
 int wave64_step(const StepArgs& P, int compute, void* stream);
 
-// body-space (primal) contact-structured path: one wave per scene, <= 64 contacts, nz + neq <= 56 - lcp_primal.hip
+// body-space (primal) contact-structured path: one wave per scene, <= 64 contacts, nz + neq <= 64 - lcp_primal.hip
 bool primal_supported(int nz, int m, int e);          // contact-list entry points: up to 24 equality rows (nz + neq <= 56), up to 64 rows with at most 4 (round 6)
-bool primal_poststab_supported(int nz, int m, int e); // post-stabilisation: nz + neq <= 56
-bool primal_dense_supported(int nz, int m, int e);    // dense boundary, post-stabilisation: up to 4
+bool primal_poststab_supported(int nz, int m, int e); // post-stabilisation: the sizes of primal_supported
+bool primal_dense_supported(int nz, int m, int e);    // dense boundary: up to 4 equality rows, nz + neq <= 56
 size_t primal_ws_bytes();
 int primal_step(const StepArgs& P, void* stream, bool pinned = false);      // pinned: LCP_HINT_PINNED (lcp_primal_pin.hip)
 int primal_step_backward(const StepArgs& P, const StepBwdArgs& G, void* stream, bool pinned = false);

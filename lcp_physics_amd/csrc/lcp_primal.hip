@@ -80,27 +80,15 @@ int primal_step_backward(const StepArgs& SP, const StepBwdArgs& Gd, void* stream
 
 // dense boundary: the scenes lcp_classify_big marked 3 (launched next to the contact-space and generic kernels, which take 2 and 0)
 int primal_dense_forward(const FwdArgs& P, int32_t* cls, size_t ws_scene, void* stream) {
-  DenseIO DN = {};
-  DN.nz = P.nz; DN.m = P.m; DN.cls = cls; DN.ws_scene = ws_scene;
-  DN.Q = (const float*)P.Q; DN.p = (const float*)P.p; DN.G = (const float*)P.G; DN.h = (const float*)P.h;
-  DN.A = (const float*)P.A; DN.b = (const float*)P.b; DN.F = (const float*)P.F;
-  StepArgs SP = {};
-  SP.B = P.B; SP.nb = P.nz / 3; SP.nc = P.m / 4; SP.e = P.e; SP.ws = P.ws;
-  SP.eps = P.eps; SP.max_iter = P.max_iter; SP.lim = P.lim;
-  SP.v_new = P.x; SP.z = P.z; SP.s = P.s; SP.y = P.y; SP.iters = P.iters; SP.status = P.status;
-  SP.tag = P.tag; SP.tag_value = P.tag_value;
+  const DenseIO DN = dense_io(P, cls, ws_scene);
+  const StepArgs SP = dense_step_args(P, P.nz / 3);
   StepBwdArgs Gd = {};
   if (primal_pin_supported(P.nz, P.e)) { const int rc = primal_pin_dense_launch(SP, DN, 0, stream); if (rc) return rc; }   // class 4: the pinned form
   return primal_dispatch<false, true>(SP, Gd, stream, DN);
 }
 int primal_dense_backward(const BwdArgs& P, int32_t* cls, size_t ws_scene, void* stream) {
-  DenseIO DN = {};
-  DN.nz = P.nz; DN.m = P.m; DN.cls = cls; DN.ws_scene = ws_scene;
-  DN.G = (const float*)P.G; DN.A = (const float*)P.A; DN.dl_dx = (const float*)P.dl_dx;
-  DN.dQ = (float*)P.dQ; DN.dp = (float*)P.dp; DN.dG = (float*)P.dG; DN.dh = (float*)P.dh; DN.dA = (float*)P.dA; DN.db = (float*)P.db; DN.dF = (float*)P.dF;
-  StepArgs SP = {};
-  SP.B = P.B; SP.nb = P.nz / 3; SP.nc = P.m / 4; SP.e = P.e; SP.ws = P.ws;
-  SP.tag = (int32_t*)P.tag; SP.tag_value = P.tag_value;
+  const DenseIO DN = dense_io(P, cls, ws_scene);
+  const StepArgs SP = dense_step_args(P, P.nz / 3);
   StepBwdArgs Gd = {};
   if (primal_pin_supported(P.nz, P.e)) { const int rc = primal_pin_dense_launch(SP, DN, 1, stream); if (rc) return rc; }
   return primal_dispatch<true, true>(SP, Gd, stream, DN);

@@ -58,7 +58,7 @@ __global__ void __launch_bounds__(64, (NCOL <= 24 ? 2 : (NCOL <= 40 ? LCP_PRIMAL
   // Round 6 (profiles/r06_ab_bwd_split.txt, item 3): what the prologue reads at addresses that depend on the lane alone is asked for HERE, without
   // lane predicates (the address is clamped, the value masked where it is used) - a load under `if (lane < ...)` is waited for at the join of
   // its branch, and the kernel used to make 17 .. 38 such round trips one after the other in front of its first multiplication
-  const int lx = lane < nz ? lane : 0;                                     // (nz <= 56: an entry that exists)
+  const int lx = lane < nz ? lane : 0;                                     // (nz <= 64: an entry that exists)
   float md_l = 0.f, vv_l = 0.f, ff_l = 0.f;
   if constexpr (!DENSE) {
     md_l = ((const float*)SP.Mdiag)[(size_t)scene * nz + lx]; vv_l = ((const float*)SP.v)[(size_t)scene * nz + lx];

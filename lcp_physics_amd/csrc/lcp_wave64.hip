@@ -1318,7 +1318,6 @@ int wave64_step(const StepArgs& SP, int compute, void* stream) {
   FwdArgs P = {};
   hipStream_t st = (hipStream_t)stream;
   const dim3 blk(64 * w64::WPB);
-  if (quad_supported(3 * SP.nb, 4 * SP.nc, SP.e)) return quad_step(SP, compute, stream);
   if (compute == LCP_COMPUTE_F64) {
     const int lw = (int)w64_lds<double>(false);
     LCP_W64_LAUNCH((w64::lcp_fwd_wave<float, double, true, true, true>), w64_grid(SP.B), lw, P, SP, lw, 0);
