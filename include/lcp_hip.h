@@ -422,6 +422,25 @@ int lcp_contact_frame_backward_nv_f64(int B, int nb, int maxc, int nvcap, int sc
                                       const float* g_n, const float* g_p1, const float* g_p2,
                                       double* dp, void* stream);
 
+/* Backward of the contact frame with respect to the SHAPE of the bodies: what the reference obtains by autograd when
+ * Circle.rad (physics/bodies.py:121) or Hull.verts (bodies.py:168-171, turned by rotate_verts, bodies.py:211-214) are leaves -
+ * every operation of DiffContactHandler (physics/contacts.py:57-352) is a torch op on those tensors, edge lengths and edge
+ * normals included.  Same inputs and sizes as lcp_contact_frame_backward_nv_f64 (nb <= 64, 8 <= nvcap <= 64, scene_verts_max <=
+ * 1024; nvcap = 8 is the layout of the lcp_move_find_contacts_f64 family, so this one entry serves both), every record type,
+ * along the branches the detection took.
+ *   out: d_radius[B,nb] and d_verts_local[B,nb,nvcap,2] (body frame: the world-frame term turned back by R(rot)^T), either may
+ *        be NULL; written, not accumulated: circles get zero vertex gradient, hulls zero radius gradient, vertex slots >= nverts
+ *        zero, and a scene whose vertices exceed scene_verts_max zeros throughout.
+ * One lane per (contacting pair, shape coordinate its records were built from: two radii, the reference edge's and the incident
+ * edge's or GJK simplex's vertices - at most 10) over the first min(count, maxc) records, summed in record order (no atomics:
+ * deterministic).  LCP_E_TOOLARGE beyond those sizes or when the LDS (40 B per vertex + 112 B per contact slot) exceeds 152 KB. */
+int lcp_contact_frame_backward_shape_f64(int B, int nb, int maxc, int nvcap, int scene_verts_max,
+                                         const int32_t* kind, const double* radius, const double* verts_local,
+                                         const int32_t* nverts, const double* p, double eps, const int32_t* count,
+                                         const int32_t* c_i1, const int32_t* c_i2,
+                                         const float* g_n, const float* g_p1, const float* g_p2,
+                                         double* d_radius, double* d_verts_local, void* stream);
+
 /* ---- debugging / A-B aids (not part of the drop-in surface) ----
  * lcp_debug_set_trace: when non-NULL, the dense forward writes trace[B, max_iter, 4] =
  *   (resid, mu, sigma, alpha) per PDIPM iteration (device pointer to doubles).

@@ -64,6 +64,7 @@ SIGNATURES = {
     "lcp_move_find_contacts_nv_f64": (_I, [_I] * 5 + [_P] * 7 + [_c.c_double, _c.c_double, _I, _I, _c.c_double,
                                                              _c.c_double] + [_P] * 12 + [_P]),
     "lcp_contact_frame_backward_nv_f64": (_I, [_I] * 5 + [_P] * 6 + [_c.c_double] + [_P] * 7 + [_P]),
+    "lcp_contact_frame_backward_shape_f64": (_I, [_I] * 5 + [_P] * 5 + [_c.c_double] + [_P] * 8 + [_P]),
     "lcp_joint_jacobian_backward_f64": (_I, [_I] * 4 + [_P] * 6 + [_P, _P, _P]),
     "lcp_state_update_backward_f64": (_I, [_I] * 3 + [_P] * 5 + [_c.c_double] + [_P] * 3 + [_P]),
     "lcp_debug_set_trace": (None, [_P]),

@@ -596,4 +596,15 @@ int lcp_contact_frame_backward_nv_f64(int B, int nb, int maxc, int nvcap, int sc
                                                  c_i1, c_i2, g_n, g_p1, g_p2, dp, stream);
 }
 
+int lcp_contact_frame_backward_shape_f64(int B, int nb, int maxc, int nvcap, int scene_verts_max, const int32_t* kind, const double* radius,
+                                         const double* verts_local, const int32_t* nverts, const double* p, double eps,
+                                         const int32_t* count, const int32_t* c_i1, const int32_t* c_i2, const float* g_n,
+                                         const float* g_p1, const float* g_p2, double* d_radius, double* d_verts_local, void* stream) {
+  if (B <= 0 || nb <= 0 || maxc <= 0 || scene_verts_max < 0) return LCP_E_BADARG;
+  if (!kind || !radius || !verts_local || !nverts || !p || !count || !c_i1 || !c_i2 || !g_n || !g_p1 || !g_p2) return LCP_E_BADARG;
+  if (!d_radius && !d_verts_local) return LCP_E_BADARG;         // (nothing asked for)
+  return lcp::contact_frame_backward_shape_launch(B, nb, maxc, nvcap, scene_verts_max, kind, radius, verts_local, nverts, p, eps, count,
+                                                  c_i1, c_i2, g_n, g_p1, g_p2, d_radius, d_verts_local, stream);
+}
+
 }  // extern "C"

@@ -6,6 +6,8 @@
 // A body's vertex / normal / edge-length arrays are read through the types VRef and SRef: plain pointers unless the includer
 // defines LCP_GEOM_VREF / LCP_GEOM_SREF (types with operator[](int) returning V2 / LCP_S; lcp_contacts_wide.hip forms the dual
 // vertices of its frame backward on read from staged values that way).
+// With LCP_GEOM_TRACE defined, the first record of a pair also names the vertices it was built from (lcp_contacts_shape.hip
+// seeds its derivative with respect to the shape with them); nothing else changes, and without the macro nothing at all.
 struct V2 { LCP_S x, y; };
 __device__ __forceinline__ V2 v2(LCP_S x, LCP_S y) { V2 r; r.x = x; r.y = y; return r; }
 __device__ __forceinline__ V2 operator+(V2 a, V2 b) { return v2(a.x + b.x, a.y + b.y); }
@@ -38,7 +40,15 @@ struct Body {             // world frame
   SRef elen;              // length of edge k
 };
 
+#ifdef LCP_GEOM_TRACE
+// tref: the body of the pair (0 / 1) that owns the vertices tr0, tr1 (the reference edge of hull / hull; the GJK simplex or the
+// SAT edge of the hull of circle / hull); ti0, ti1: the incident edge's vertices, on the other body.  -1: none.
+struct Pt { V2 n, p1, p2; LCP_S pen; int tref, tr0, tr1, ti0, ti1; };
+#define LCP_TRACE(pt, b, r0, r1, i0, i1) do { (pt).tref = (b); (pt).tr0 = (r0); (pt).tr1 = (r1); (pt).ti0 = (i0); (pt).ti1 = (i1); } while (0)
+#else
 struct Pt { V2 n, p1, p2; LCP_S pen; };
+#define LCP_TRACE(pt, b, r0, r1, i0, i1) do { } while (0)
+#endif
 
 // contacts.py:207-217 (`>=`: last maximiser wins)
 __device__ __forceinline__ int support(VRef pts, int n, V2 dir) {
@@ -55,6 +65,7 @@ __device__ __forceinline__ int circle_circle(const Body& b1, const Body& b2, dou
   if (pen < -eps) return 0;
   n = n * (1.0 / dist);
   out0.n = n; out0.p1 = -n * (b1.rad - pen / 2); out0.p2 = n * (b2.rad - pen / 2); out0.pen = pen;
+  LCP_TRACE(out0, 0, -1, -1, -1, -1);
   return 1;
 }
 
@@ -128,6 +139,7 @@ __device__ __forceinline__ int circle_hull(const Body& circ, const Body& hull, d
     sx.n = keep.n + 1;
   }
   V2 bn, bp1, bp2; LCP_S bd;
+  LCP_TRACE(out0, circle_is_g2 ? 0 : 1, keep.ia, keep.n == 2 ? keep.ib : -1, -1, -1);
   if (keep.n < 3) {
     bp2 = cl;
     const V2 cw = cl + hull.pos;
@@ -146,6 +158,7 @@ __device__ __forceinline__ int circle_hull(const Body& circ, const Body& hull, d
         bd = dist; bn = nrm;
         bp2 = center + nrm * -(dist + circ.rad);
         bp1 = bp2 + hull.pos - circ.pos;
+        LCP_TRACE(out0, circle_is_g2 ? 0 : 1, idx, (idx + 1) % nv, -1, -1);
       }
     }
   }
@@ -235,6 +248,7 @@ __device__ __forceinline__ int hull_hull(const Body& b1, const Body& b2, double 
       ++n;
     }
   }
+  if (n > 0) LCP_TRACE(out0, ref_is_b2 ? 1 : 0, c.edge, (c.edge + 1) % ref.nv, ie, (ie + 1) % inc.nv);
   return n;
 }
 
@@ -245,4 +259,4 @@ __device__ __forceinline__ int collide_pair(const Body& b1, const Body& b2, doub
   if (c2) return circle_hull(b2, b1, eps, true, out0);
   return hull_hull(b1, b2, eps, out0, out1);
 }
-
+#undef LCP_TRACE

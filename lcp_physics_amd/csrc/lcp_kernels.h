@@ -232,5 +232,12 @@ int contact_frame_backward_wide_launch(int B, int nb, int maxc, int nvcap, int s
                                        const double* radius, const double* verts_local, const int32_t* nverts, const double* p,
                                        double eps, const int32_t* count, const int32_t* c_i1, const int32_t* c_i2,
                                        const float* g_n, const float* g_p1, const float* g_p2, double* dp, void* stream);
+// backward of the contact frame with respect to the SHAPE (radii, body-frame hull vertices) at the same sizes: one lane per
+// (contacting pair, shape coordinate the pair's records were built from) - lcp_contacts_shape.hip
+int contact_frame_backward_shape_launch(int B, int nb, int maxc, int nvcap, int scene_verts_max, const int32_t* kind,
+                                        const double* radius, const double* verts_local, const int32_t* nverts, const double* p,
+                                        double eps, const int32_t* count, const int32_t* c_i1, const int32_t* c_i2,
+                                        const float* g_n, const float* g_p1, const float* g_p2, double* d_radius,
+                                        double* d_verts_local, void* stream);
 
 }  // namespace lcp

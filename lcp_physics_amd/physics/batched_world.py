@@ -771,7 +771,11 @@ class ContactWorld:
         # increment is zero (bodies.py:199-202 `if rot.item() != 0: self.rotate_verts(rot)`), so its autograd has no
         # vertex path through such a step (a hull in free fall with no torque on it, for instance)
         p_geo = self._p_geom if getattr(self, "_p_geom_src", None) is self.p else self.p
-        c_n, c_p1, c_p2 = ct.ContactFrameFunction.apply(p_geo, self.geom, frame, self.eps)
+        # the shape as an input of the frame nodes where it requires grad (lcp_contact_frame_backward_shape_f64); the detection
+        # launches read its values through raw pointers either way
+        shape_in = tuple(t if t.requires_grad else None for t in (self.geom.radius, self.geom.verts_local))
+        shape_in = shape_in if any(t is not None for t in shape_in) else ()
+        c_n, c_p1, c_p2 = ct.ContactFrameFunction.apply(p_geo, self.geom, frame, self.eps, *shape_in)
         f = self.f if self.force_fn is None else self.force_fn(self.t).to(torch.float32).contiguous()
         opts = {"max_iter": self.max_iter, "eps": self.solver_eps, "not_improved_lim": self.lim, "compute": self.compute,
                 "pinned": self._pinned}
@@ -807,7 +811,7 @@ class ContactWorld:
             frame2 = cb                                                    # (retired like `frame`: the detection at the end fills a fresh set)
             frame2.retired = True
             dt_used = cb.dt_used
-            g_n, g_p1, g_p2 = ct.ContactFrameFunction.apply(self._p_geom, self.geom, frame2, self.eps)
+            g_n, g_p1, g_p2 = ct.ContactFrameFunction.apply(self._p_geom, self.geom, frame2, self.eps, *shape_in)
             pose_dep = js is not None and js.pose_dependent
             Je2 = _JointJacobianFn.apply(self.p, self._jrot_ad, js.jr1, js, self.Je) if pose_dep else self.Je
             p_corr = torch.empty_like(cb.p_out)                            # the corrected pose: the kernel's own move, as in step()

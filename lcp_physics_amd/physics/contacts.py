@@ -36,7 +36,14 @@ class GeometryBatch:
     uint8 or None (the pairs `World` excludes through `add_no_contact`, bodies.py:117-118).
     scene_verts_max: the largest sum of hull vertices over one scene (a host int: it sizes the LDS of the wide kernels);
     `from_shapes` sets it, otherwise it is computed on first use (one synchronisation) and cached - rebuild the batch
-    rather than editing `nverts` in place."""
+    rather than editing `nverts` in place.
+
+    `radius` and `verts_local` may require grad (or carry a graph: one learnable shape expanded over the B scenes, say):
+    `ContactWorld.step(differentiable=True)` then back-propagates to them through the contact frame
+    (`contact_frame_backward_shape`), as the reference's autograd does to `Circle.rad` / `Hull.verts`.  The kernels read
+    their values only.  What stays the caller's job, as in the reference's `Hull.__init__`: vertices that are convex,
+    counter-clockwise and centred on the centroid - and the dependence of `Mdiag` on the shape (inertia of a disc or a
+    polygon), which is plain torch on the same leaves and composes with the `Mdiag` gradient of the step."""
     kind: torch.Tensor
     radius: torch.Tensor
     verts_local: torch.Tensor
@@ -70,20 +77,25 @@ class GeometryBatch:
         return self.nvcap != NV or self.nb > NB_SMALL
 
     def to(self, device):
-        mv = lambda t: None if t is None else t.to(device).contiguous()
+        mv = lambda t: None if t is None else t.to(device).contiguous()     # (differentiable: a graph on radius / verts_local survives)
         return GeometryBatch(mv(self.kind), mv(self.radius), mv(self.verts_local), mv(self.nverts), mv(self.no_contact),
                              self.scene_verts_max)
 
     @staticmethod
     def from_shapes(shapes, B=1, max_verts=NV):
         """`shapes`: per body ('circle', rad) or ('rect', (w, h)) or ('hull', verts[nv,2]); replicated B times.
+        A radius or a vertex array given as a tensor that requires grad stays connected: `radius` / `verts_local` of the
+        batch are then functions of it (autograd sums over the B replicas).
         `max_verts`: the vertex capacity of `verts_local` (8 .. 64; a larger hull raises ValueError); None: the largest hull's
         vertex count, at least 8."""
         nb = len(shapes)
         vlists = []
+        live = lambda a: isinstance(a, torch.Tensor) and a.requires_grad
         for k, a in shapes:
             if k == "circle":
                 vlists.append(None)
+            elif live(a) and k != "rect":
+                vlists.append(a.detach().to(torch.float64).tolist())
             elif k == "rect":                        # bodies.py:261-264: [half, half * (-1, 1), -half, -half * (-1, 1)]
                 hw, hh = float(a[0]) / 2, float(a[1]) / 2
                 vlists.append([[hw, hh], [-hw, hh], [-hw, -hh], [hw, -hh]])
@@ -99,12 +111,17 @@ class GeometryBatch:
         nverts = torch.zeros(nb, dtype=torch.int32)
         for i, ((k, a), vs) in enumerate(zip(shapes, vlists)):
             if k == "circle":
-                kind[i], radius[i] = CIRCLE, float(a)
+                kind[i], radius[i] = CIRCLE, float(a.detach() if live(a) else a)
             else:
                 if len(vs) > cap:
                     raise ValueError("hulls are limited to %d vertices" % cap)
                 kind[i], nverts[i] = HULL, len(vs)
                 verts[i, :len(vs)] = torch.tensor(vs, dtype=torch.float64)
+        for i, (k, a) in enumerate(shapes):                  # learnable shapes: the same values, with their graph
+            if live(a) and k == "circle":
+                radius = radius.index_put((torch.tensor(i),), a.to(torch.float64).reshape(()))
+            elif live(a) and k != "rect":
+                verts = torch.cat([verts[:i], torch.cat([a.to(torch.float64), verts[i, a.shape[0]:]]).unsqueeze(0), verts[i + 1:]])
         rep = lambda t: t.unsqueeze(0).repeat(B, *([1] * t.dim())).contiguous()
         return GeometryBatch(rep(kind), rep(radius), rep(verts), rep(nverts), None, int(nverts.sum()))
 
@@ -229,6 +246,33 @@ def contact_frame_backward(geom, p, cb, g_n, g_p1, g_p2, eps=EPSILON):
     return dp
 
 
+def contact_frame_backward_shape(geom, p, cb, g_n, g_p1, g_p2, eps=EPSILON, want_radius=True, want_verts=True):
+    """d(loss)/d(radius) [B,nb] and d(loss)/d(verts_local) [B,nb,cap,2] through the contact frame
+    (`lcp_contact_frame_backward_shape_f64`, lcp_contacts_shape.hip): what the reference's autograd gives `Circle.rad` and
+    `Hull.verts` (`contacts.py:57-352` on `bodies.py:121, 168-171, 211-214`) for the contacts in `cb` detected at pose `p` with margin
+    `eps`, along the branches the detection took.  One kernel for every geometry layout (capacity 8 .. 64, up to 64 bodies).
+    Circles get zero vertex gradient, hulls zero radius gradient, vertex slots beyond `nverts` zero.  An output that is not
+    wanted is None."""
+    lib = _lib.load()
+    B, nb = geom.B, geom.nb
+    dev = p.device
+    for name, t in (("g_n", g_n), ("g_p1", g_p1), ("g_p2", g_p2)):
+        _lib.require_gpu_tensor(t, name, torch.float32)
+    _lib.require_gpu_tensor(p, "p", torch.float64)
+    radius, verts = geom.radius.detach(), geom.verts_local.detach()
+    _lib.require_gpu_tensor(radius, "radius", torch.float64)
+    _lib.require_gpu_tensor(verts, "verts_local", torch.float64)
+    d_rad = torch.empty(B, nb, dtype=torch.float64, device=dev) if want_radius else None
+    d_verts = torch.empty(B, nb, geom.nvcap, 2, dtype=torch.float64, device=dev) if want_verts else None
+    P = _lib.ptr
+    with torch.cuda.device(dev):
+        rc = lib.lcp_contact_frame_backward_shape_f64(B, nb, cb.c_n.shape[1], geom.nvcap, geom.verts_max(), P(geom.kind), P(radius),
+                                                      P(verts), P(geom.nverts), P(p), float(eps), P(cb.count), P(cb.c_i1), P(cb.c_i2),
+                                                      P(g_n), P(g_p1), P(g_p2), P(d_rad), P(d_verts), _lib.stream_ptr(dev))
+    _lib.check(rc, "lcp_contact_frame_backward_shape_f64")
+    return d_rad, d_verts
+
+
 class _FrameSnapshot:
     __slots__ = ("c_n", "c_p1", "c_p2", "c_i1", "c_i2", "count")
 
@@ -237,10 +281,14 @@ class ContactFrameFunction(torch.autograd.Function):
     """The contact list as a differentiable function of the poses: forward hands out the records the detection kernel
     found at `p` (their values are constants of the launch), backward is `lcp_contact_frame_backward_f64`.
 
-        c_n, c_p1, c_p2 = ContactFrameFunction.apply(p, geom, frame)        # frame: a snapshot of the ContactBuffers"""
+        c_n, c_p1, c_p2 = ContactFrameFunction.apply(p, geom, frame)        # frame: a snapshot of the ContactBuffers
+
+    With the optional trailing inputs `radius`, `verts_local` (pass `geom.radius` / `geom.verts_local` where they require grad, None
+    otherwise) the records are functions of the shape too: backward then also runs `lcp_contact_frame_backward_shape_f64`.  Without
+    them - or when neither needs a gradient - the backward is the pose kernel's launch alone."""
 
     @staticmethod
-    def forward(ctx, p, geom, frame, eps=EPSILON):
+    def forward(ctx, p, geom, frame, eps=EPSILON, radius=None, verts_local=None):
         # The kernels write contact buffers through raw pointers (autograd's version counters never see it), so the records this node
         # hands out and keeps for its backward must belong to nobody else: a `snapshot_frame()`, or the ContactBuffers a
         # differentiable step RETIRED (`ContactWorld.step_autograd` marks them `retired`: the world detects into a fresh set from
@@ -256,8 +304,15 @@ class ContactFrameFunction(torch.autograd.Function):
         (p,) = ctx.saved_tensors
         z = lambda g, like: torch.zeros_like(like) if g is None else g.contiguous()
         fr = ctx.frame
-        dp = contact_frame_backward(ctx.geom, p, fr, z(g_n, fr.c_n), z(g_p1, fr.c_p1), z(g_p2, fr.c_p2), eps=ctx.eps)
-        return dp, None, None, None
+        g_n, g_p1, g_p2 = z(g_n, fr.c_n), z(g_p1, fr.c_p1), z(g_p2, fr.c_p2)
+        dp = contact_frame_backward(ctx.geom, p, fr, g_n, g_p1, g_p2, eps=ctx.eps) if ctx.needs_input_grad[0] else None
+        d_rad = d_verts = None
+        need = tuple(ctx.needs_input_grad) + (False, False)             # (as many entries as `apply` was given inputs)
+        want_r, want_v = need[4], need[5]
+        if want_r or want_v:
+            d_rad, d_verts = contact_frame_backward_shape(ctx.geom, p, fr, g_n, g_p1, g_p2, eps=ctx.eps, want_radius=want_r,
+                                                          want_verts=want_v)
+        return (dp, None, None, None, d_rad, d_verts)[:len(ctx.needs_input_grad)]
 
 
 def snapshot_frame(cb):
