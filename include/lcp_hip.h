@@ -52,7 +52,8 @@ extern "C" {
 #define LCP_PATH_PRIMAL 0x4000
 /* Likewise: the contact-list step on one workgroup per scene in body space (lcp_primal_wg.hip) wherever its sizes allow - at most 128
  * pivots (3 nb - 3 under LCP_HINT_PINNED with e = 3, else 3 nb + e with e <= 4), at most 256 contacts, fp64 arithmetic - also where
- * another family would serve the call by default (A/B aid; the backward must carry the same bit). */
+ * another family would serve the call by default (A/B aid; the backward must carry the same bit).  lcp_post_stabilization_f32 and its
+ * backward follow the bit too (lcp_primal_wg_poststab.hip: 3 nb + e <= 128 with e <= 4, at most 256 contacts). */
 #define LCP_PATH_PRIMAL_WG 0x80000
 /* Contact-list forwards of the four-scenes-per-wave sizes choose by batch size between four scenes per wavefront (lcp_quad.hip) and
  * one scene per wavefront (lcp_solo.hip, small batches); these force one of the two (A/B aids; same workspace layout, any backward
@@ -273,8 +274,12 @@ int lcp_solve_dynamics_f32(int B, int nb, int maxc, int e, const int32_t* c_coun
  * dt_k = dt_scene[k] (the dt the scene's step ended up using; NULL: the scalar `dt`) - world.py:110-117; the caller
  * re-detects contacts at p_out (world.py:121: lcp_move_find_contacts_f64 with v = NULL); p_out may be p itself.
  * Runs on the wave-per-scene body-space kernel (fp64 arithmetic, maxc <= 64, e <= 24, 3 nb + e <= 56, or e <= 4 with 3 nb + e <= 64; it leaves its best
- * iterate in the workspace for lcp_post_stabilization_backward_f32) or on the workgroup-per-scene generic kernels (any size
- * their plan takes: LCP_E_TOOLARGE beyond); workspace of lcp_workspace_bytes(B, 3 nb, 4 maxc, e, compute).
+ * iterate in the workspace for lcp_post_stabilization_backward_f32); beyond those sizes on the workgroup-per-scene BODY-space kernel
+ * (lcp_primal_wg_poststab.hip: fp64 arithmetic, 3 nb + e <= 128 with e <= 4 - 41 bodies on a three-row floor -, maxc <= 256; one
+ * workgroup of 256 threads per scene, the system in LDS, its own workspace layout and tag) where the capacity is at least three
+ * contact slots per two bodies (4 maxc >= 6 nb: below that the generic kernels are as fast) or LCP_PATH_PRIMAL_WG asks for it; else on
+ * the workgroup-per-scene generic kernels (any size their plan takes: LCP_E_TOOLARGE beyond); workspace of
+ * lcp_workspace_bytes(B, 3 nb, 4 maxc, e, compute).
  *   out: dp[B,nb,3]  p_out[B,nb,3] (optional)  iters[B]  status[B] */
 int lcp_post_stabilization_f32(int B, int nb, int maxc, int e, const int32_t* c_count,
                                const float* Mdiag, const float* v, const float* rest,
@@ -288,7 +293,9 @@ int lcp_post_stabilization_f32(int B, int nb, int maxc, int e, const int32_t* c_
  * through PdipmEngine.post_stabilization (engines.py:80-116: ge = Je v, gc = Jc v + Jc v * -restitutions, the LCPFunction
  * call and its backward lcp.py:37-64, dp = -x) when a World with post_stab=True is differentiated (experiments/inference.py).
  * Must follow the forward on the same stream with the same workspace and unchanged inputs.  Body-space kernel where the forward
- * ran there (fp64 arithmetic, maxc <= 64, e <= 24, 3 nb + e <= 56, or e <= 4 with 3 nb + e <= 64), else (round 6) the generic kernels on the iterate
+ * ran there (fp64 arithmetic, maxc <= 64, e <= 24, 3 nb + e <= 56, or e <= 4 with 3 nb + e <= 64: one wave per scene; beyond them
+ * 3 nb + e <= 128 with e <= 4 and maxc <= 256: one workgroup per scene, lcp_primal_wg_poststab.hip - the same `compute` word picks
+ * the same family), else (round 6) the generic kernels on the iterate
  * lcp_post_stab_kernel keeps - any size of their plan, either arithmetic; LCP_E_TOOLARGE beyond it.
  *   in : the forward's inputs, dl_ddp[B,nb,3] = d(loss)/d(dp)
  *   out: dMdiag[B,nb,3] dv[B,nb,3] drest[B,nb] dc_n[B,maxc,2] dc_p1[B,maxc,2] dc_p2[B,maxc,2] dJe[B,e,3nb]

@@ -59,7 +59,8 @@ enum WsTag {
   TAG_STEP_QUAD_BODY = 4, TAG_STEP_QUAD_CS = 5, TAG_STEP_PRIMAL = 6, TAG_STEP_BIG = 7, TAG_STEP_WAVE64 = 8, TAG_STEP_GENERIC = 9,
   TAG_POSTSTAB_PRIMAL = 10, TAG_POSTSTAB_GENERIC = 11,
   TAG_DENSE_WAVE_BODY = 12,                                                           // lcp_pdipm_forward_f32, class-2 scenes solved in body space (no W)
-  TAG_STEP_PRIMAL_WG = 13                                                             // contact-list step, one workgroup per scene in body space
+  TAG_STEP_PRIMAL_WG = 13,                                                            // contact-list step, one workgroup per scene in body space
+  TAG_POSTSTAB_PRIMAL_WG = 14                                                         // post-stabilisation, one workgroup per scene in body space
 };
 constexpr size_t TRAILER_BYTES = 256;
 
@@ -136,12 +137,21 @@ inline Route route_step(int nz, int m, int e, const Word& w, bool has_counts) {
 }
 
 // lcp_post_stabilization_*: body space where the sizes allow (lcp_quad.hip in automatic mode where it takes them, lcp_primal.hip
-// otherwise - one layout, one tag, one backward), the generic kernels everywhere else
+// otherwise - one layout, one tag, one backward; beyond one wavefront lcp_primal_wg_poststab.hip with a layout and a tag of its
+// own), the generic kernels everywhere else
 inline Route route_poststab(int nz, int m, int e, const Word& w) {
   Route r = route_base(nz, m, e, w);
   const bool body = (w.path == P_AUTO || w.path == P_PRIMAL) && w.f64() && lcp::primal_poststab_supported(nz, m, e);
-  r.fam = !body ? FAM_GENERIC : (w.path == P_AUTO && lcp::quad_post_supported(nz, m, e)) ? FAM_QUAD : FAM_PRIMAL;
-  r.tag = body ? TAG_POSTSTAB_PRIMAL : TAG_POSTSTAB_GENERIC;
+  // lcp_primal_wg_poststab.hip: its sizes, fp64 arithmetic, its per-scene block within the stride the workspace already has there
+  // and only where the generic plan holds the size (lcp_workspace_bytes, lcp_post_stabilization_has_backward and LCP_E_TOOLARGE
+  // stay what they were).  Its time follows the bodies alone, the generic kernels' (one row per contact: T is maxc x maxc) the
+  // contacts: automatic mode takes it from three contact slots per two bodies on (m >= 2 nz), where it measured 1.4 x - 29 x
+  // faster; at one slot per body the two are within 20 % of each other, either way (profiles/r09_poststab_wg_sweep.json).
+  // LCP_PATH_PRIMAL_WG takes it wherever it fits, the sizes of the one-wave kernels included (A/B)
+  const bool wg_fits = w.f64() && lcp::primal_wg_poststab_supported(nz, m, e) && lcp::primal_wg_poststab_ws_bytes(m) <= r.ws_scene && r.plan.ok;
+  const bool wg = !body && wg_fits && (w.path == P_PRIMAL_WG || (w.path == P_AUTO && m >= 2 * nz));
+  r.fam = wg ? FAM_PRIMAL_WG : !body ? FAM_GENERIC : (w.path == P_AUTO && lcp::quad_post_supported(nz, m, e)) ? FAM_QUAD : FAM_PRIMAL;
+  r.tag = wg ? TAG_POSTSTAB_PRIMAL_WG : body ? TAG_POSTSTAB_PRIMAL : TAG_POSTSTAB_GENERIC;
   r.has_backward = body || r.plan.ok;
   return r;
 }
@@ -479,6 +489,7 @@ int lcp_post_stabilization_f32(int B, int nb, int maxc, int e, const int32_t* c_
   switch (r.fam) {
     case FAM_QUAD: return lcp::quad_post_stab(P, stream);
     case FAM_PRIMAL: return lcp::primal_post_stab(P, stream);
+    case FAM_PRIMAL_WG: return lcp::primal_wg_post_stab(P, stream);
     default: return r.plan.ok ? lcp::generic_post_stab(P, w.arith, r.plan.lds_bytes, stream) : LCP_E_TOOLARGE;
   }
 }
@@ -500,8 +511,8 @@ int lcp_post_stabilization_backward_f32(int B, int nb, int maxc, int e, const fl
   int rc = fill_step(P, B, nb, maxc, e, nullptr, Mdiag, v, /*f*/ v, rest, /*fric*/ rest, c_n, c_p1, c_p2, c_i1, c_i2, Je, 0.0f);
   if (rc) return rc;
   if (!dl_ddp || !ws) return LCP_E_BADARG;
-  // the forward's route: the body-space kernels where they ran, lcp_step_bwd_kernel<.., POST> on the iterate lcp_post_stab_kernel
-  // kept otherwise
+  // the forward's route: the body-space kernels where they ran (one wave or one workgroup per scene, each on its own layout),
+  // lcp_step_bwd_kernel<.., POST> on the iterate lcp_post_stab_kernel kept otherwise
   const Route r = route_poststab(3 * nb, 4 * maxc, e, w);
   if (!r.has_backward) return LCP_E_TOOLARGE;
   P.ws = ws;
@@ -509,8 +520,11 @@ int lcp_post_stabilization_backward_f32(int B, int nb, int maxc, int e, const fl
   lcp::StepBwdArgs G = {};
   G.dl_dv = dl_ddp; G.dMdiag = dMdiag; G.dv = dv; G.drest = drest; G.dcn = dc_n; G.dcp1 = dc_p1; G.dcp2 = dc_p2;
   G.dJe = (e > 0) ? dJe : nullptr;
-  if (r.fam != FAM_GENERIC) return lcp::primal_post_stab_backward(P, G, stream);
-  return lcp::generic_post_stab_backward(P, G, w.arith, r.plan.lds_bytes, stream);
+  switch (r.fam) {
+    case FAM_GENERIC: return lcp::generic_post_stab_backward(P, G, w.arith, r.plan.lds_bytes, stream);
+    case FAM_PRIMAL_WG: return lcp::primal_wg_post_stab_backward(P, G, stream);
+    default: return lcp::primal_post_stab_backward(P, G, stream);        // (lcp_quad.hip's forward leaves the one-wave layout)
+  }
 }
 
 

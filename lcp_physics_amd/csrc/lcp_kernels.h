@@ -183,6 +183,11 @@ bool primal_wg_supported(int nz, int m, int e, bool pinned);   // <= 128 pivots 
 size_t primal_wg_ws_bytes(int m);                              // per scene: contact count, best iterate (x, y, z, s)
 int primal_wg_step(const StepArgs& P, void* stream, bool pinned = false);
 int primal_wg_step_backward(const StepArgs& P, const StepBwdArgs& G, void* stream, bool pinned = false);
+// post-stabilisation on the same mapping (general form only) - lcp_primal_wg_poststab.hip
+bool primal_wg_poststab_supported(int nz, int m, int e);       // nz + neq <= 128 with neq <= 4, <= 256 contacts
+size_t primal_wg_poststab_ws_bytes(int m);                     // per scene: contact count, best iterate (x, y, z, s: one row per contact)
+int primal_wg_post_stab(const StepArgs& P, void* stream);
+int primal_wg_post_stab_backward(const StepArgs& P, const StepBwdArgs& G, void* stream);
 
 // four-scenes-per-wave contact-structured path (nc <= 16, neq <= 4, diagonal Q; nz <= 16, or nz <= 32 from a contact
 // list) - lcp_quad.hip
