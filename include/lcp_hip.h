@@ -375,7 +375,8 @@ int lcp_joint_jacobian_backward_f64(int B, int nb, int nj, int e,
  *   p_new = p + scale v dt_k (cotangent g_p);  the pose the geometry is differentiated at, geo_new = p_geo + the same increment where
  *   it is non-zero or the coordinate is x / y (cotangent g_g);  rot_new = rot + scale v[body1][0] dt_k for revolute joints (g_rot).
  * g_p / g_g [B,nb,3] float64 and g_rot [B,nj] float64 may be NULL (no such cotangent);  v[B,nb,3] float32 the velocities of the move
- * (new_v, or the post-stabilisation dp with scale = 0.5, world.py:112);  dt_scene[B] > 0 the dt each scene's step accepted;
+ * (new_v, or the post-stabilisation dp with scale = 0.5, world.py:112);  dt_scene[B] >= 0 the dt each scene's step accepted (0: a scene that
+ * was finished in a sub-step of fixed-interval stepping and did not move - its g_v is exactly 0);
  * jtype / jb1 [B,nj] as in lcp_joint_jacobian_f64 (needed with g_rot).   out: g_v[B,nb,3] float32 = d(loss)/dv. */
 int lcp_state_update_backward_f64(int B, int nb, int nj,
                                   const double* g_p, const double* g_g, const double* g_rot,
@@ -415,6 +416,44 @@ int lcp_move_find_contacts_nv_f64(int B, int nb, int maxc, int nvcap, int scene_
                                   double* p_out, float* c_n, float* c_p1, float* c_p2, double* c_pen,
                                   int32_t* c_i1, int32_t* c_i2, int32_t* count, double* max_pen,
                                   double* dt_used, double* t, int32_t* trials, void* stream);
+
+/* The move / detect / halve loop of World.step_dt (physics/world.py:88-101) when World.step(fixed_dt=True) drives it
+ * (world.py:72-80: `while self.t < end_t: self.step_dt(end_t - self.t)`): every scene starts its loop from a dt of its own.
+ * The arguments, semantics and outputs of lcp_move_find_contacts_nv_f64, plus
+ *   dt_scene[B]  (required) the dt each scene's loop starts from; the scalar `dt` is not read.  A scene with dt_scene <= 0 has
+ *                reached its end_t: it makes one trial without moving and is done whatever the penetration test says -
+ *                p_out = p_start bitwise, the records of that pose, dt_used = 0, t unchanged, trials = 1.
+ * `dt_floor` stays the caller's (world.py:98 compares with self.dt / 4, the world's dt, not the sub-step's).
+ * nb <= 32 with nvcap == 8 runs the kernels of lcp_move_find_contacts_f64, anything else those of the _nv_ entry; the size
+ * errors are the _nv_ entry's (LCP_E_TOOLARGE for nb > 64, nvcap outside [8, 64], scene_verts_max > 1024), checked before
+ * any launch.  With all dt_scene equal to a positive dt the outputs are bitwise those of the scalar entries. */
+int lcp_move_find_contacts_dts_f64(int B, int nb, int maxc, int nvcap, int scene_verts_max,
+                                   const int32_t* kind, const double* radius, const double* verts_local,
+                                   const int32_t* nverts, const uint8_t* no_contact,
+                                   const double* p_start, const float* v,
+                                   double dt, double dt_floor, int strict, int max_trials,
+                                   double eps, double tol,
+                                   double* p_out, float* c_n, float* c_p1, float* c_p2, double* c_pen,
+                                   int32_t* c_i1, int32_t* c_i2, int32_t* count, double* max_pen,
+                                   double* dt_used, double* t, int32_t* trials,
+                                   const double* dt_scene, void* stream);
+
+/* The head of one sub-step of World.step(fixed_dt=True) (physics/world.py:76-78) for B scenes, element-wise:
+ *   in : t[B], end_t[B] float64 (the scenes' clocks and the time their step ends at)  f[B,nb,3] float32 (the forces at t)
+ *        count[B] (the contacts of the current pose)
+ *   out: dt_k[B] float64 = end_t - t where t < end_t, else 0 (world.py:77, that subtraction in fp64)
+ *        active[B] int32 = t < end_t (world.py:76)
+ *        count_eff[B] = count where active, else 0 (a finished scene takes the no-contact branch of the solve, engines.py:36-50)
+ *        f_eff[B,nb,3] float32 = (float)dt_k * f, one fp32 product: lcp_solve_dynamics_f32 with dt = 1 and f_eff forms
+ *        u = M v + dt_k f (engines.py:31-32) bit for bit as it would with a dt of dt_k per scene.
+ * All outputs are required; none may alias an input. */
+int lcp_substep_begin_f64(int B, int nb, const double* t, const double* end_t, const float* f,
+                          const int32_t* count, double* dt_k, int32_t* active, int32_t* count_eff,
+                          float* f_eff, void* stream);
+
+/* The tail of the solve of one sub-step (physics/world.py:87 `set_v(new_v)`, which a finished scene never reaches):
+ * v_new[B,nb,3] = active[B] ? v_new : v_old, in place (only the entries of finished scenes are written). */
+int lcp_substep_commit_f32(int B, int nb, const int32_t* active, const float* v_old, float* v_new, void* stream);
 
 /* lcp_contact_frame_backward_f64 at the sizes of lcp_move_find_contacts_nv_f64 (nb <= 64, verts_local[B,nb,nvcap,2] with
  * 8 <= nvcap <= 64, scene_verts_max <= 1024), plus the records' body indices c_i1 / c_i2 [B,maxc] of that detection: the

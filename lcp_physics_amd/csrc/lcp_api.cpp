@@ -599,6 +599,44 @@ int lcp_move_find_contacts_nv_f64(int B, int nb, int maxc, int nvcap, int scene_
   return lcp::contacts_wide_launch(P, nvcap, scene_verts_max, stream);
 }
 
+// World.step(fixed_dt=True) (world.py:72-80): step_dt(end_t - t) with a dt of its own per scene
+int lcp_move_find_contacts_dts_f64(int B, int nb, int maxc, int nvcap, int scene_verts_max, const int32_t* kind, const double* radius,
+                                   const double* verts_local, const int32_t* nverts, const uint8_t* no_contact,
+                                   const double* p_start, const float* v, double dt, double dt_floor, int strict,
+                                   int max_trials, double eps, double tol, double* p_out, float* c_n, float* c_p1,
+                                   float* c_p2, double* c_pen, int32_t* c_i1, int32_t* c_i2, int32_t* count,
+                                   double* max_pen, double* dt_used, double* t, int32_t* trials, const double* dt_scene, void* stream) {
+  if (B <= 0 || nb <= 0 || maxc <= 0 || max_trials <= 0 || scene_verts_max < 0) return LCP_E_BADARG;
+  if (!kind || !radius || !verts_local || !nverts || !p_start || !dt_scene) return LCP_E_BADARG;
+  if (!c_n || !c_p1 || !c_p2 || !c_i1 || !c_i2 || !count) return LCP_E_BADARG;
+  lcp::ContactArgs P;
+  memset(&P, 0, sizeof(P));
+  P.B = B; P.nb = nb; P.maxc = maxc; P.kind = kind; P.nverts = nverts; P.radius = radius;
+  P.verts_local = verts_local; P.no_contact = no_contact; P.p_start = p_start; P.v = v;
+  P.dt = dt; P.dt_floor = dt_floor; P.eps = eps; P.tol = tol; P.strict = strict; P.max_trials = max_trials;
+  P.p_out = p_out; P.c_n = c_n; P.c_p1 = c_p1; P.c_p2 = c_p2; P.c_pen = c_pen; P.c_i1 = c_i1; P.c_i2 = c_i2;
+  P.count = count; P.max_pen = max_pen; P.dt_used = dt_used; P.t = t; P.trials = trials;
+  P.dt_in = dt_scene;
+  // (the limits of lcp_move_find_contacts_nv_f64, whichever kernel serves the call)
+  if (nb > 64 || nvcap < 8 || nvcap > 64 || scene_verts_max > lcp::CONTACTS_WIDE_MAX_SCENE_VERTS) return LCP_E_TOOLARGE;
+  if (nb <= 32 && nvcap == 8) return lcp::contacts_launch(P, stream);
+  return lcp::contacts_wide_launch(P, nvcap, scene_verts_max, stream);
+}
+
+// the bookkeeping of world.py:72-80 around one sub-step (lcp_substep.hip)
+int lcp_substep_begin_f64(int B, int nb, const double* t, const double* end_t, const float* f, const int32_t* count, double* dt_k,
+                          int32_t* active, int32_t* count_eff, float* f_eff, void* stream) {
+  if (B <= 0 || nb <= 0) return LCP_E_BADARG;
+  if (!t || !end_t || !f || !count || !dt_k || !active || !count_eff || !f_eff) return LCP_E_BADARG;
+  return lcp::substep_begin_launch(B, nb, t, end_t, f, count, dt_k, active, count_eff, f_eff, stream);
+}
+
+int lcp_substep_commit_f32(int B, int nb, const int32_t* active, const float* v_old, float* v_new, void* stream) {
+  if (B <= 0 || nb <= 0) return LCP_E_BADARG;
+  if (!active || !v_old || !v_new) return LCP_E_BADARG;
+  return lcp::substep_commit_launch(B, nb, active, v_old, v_new, stream);
+}
+
 int lcp_contact_frame_backward_nv_f64(int B, int nb, int maxc, int nvcap, int scene_verts_max, const int32_t* kind, const double* radius,
                                       const double* verts_local, const int32_t* nverts, const uint8_t* no_contact, const double* p,
                                       double eps, const int32_t* count, const int32_t* c_i1, const int32_t* c_i2, const float* g_n,

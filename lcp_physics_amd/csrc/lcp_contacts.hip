@@ -68,7 +68,9 @@ __device__ __forceinline__ bool operator==(Dual a, Dual b) { return a.v == b.v; 
 // scene has at most 16 body pairs, i.e. nb <= 6 - the common case; the lanes of a scene are one DPP/shuffle row).
 // Scenes that share a wave advance in lock step: a scene whose step is accepted keeps recomputing the same accepted
 // trial (identical stores) until its neighbours are done.
-template <int LPS, int NBMAX>
+// DTS: the loop of every scene starts from P.dt_in[scene] (World.step(fixed_dt=True), world.py:72-80); a compile-time choice, so that the
+// scalar-dt instantiations are the code they were (with a run-time test they measured 3 % slower on the 4-box world: profiles/r10_fixed_dt.json).
+template <int LPS, int NBMAX, bool DTS>
 __global__ void __launch_bounds__(64) lcp_move_find_contacts_kernel(ContactArgs P) {
   constexpr int SPW = 64 / LPS;                                 // scenes per wave
   static_assert(NBMAX <= MAXB && (LPS == 64 || NBMAX * (NBMAX - 1) / 2 <= LPS), "bodies per scene");
@@ -95,7 +97,8 @@ __global__ void __launch_bounds__(64) lcp_move_find_contacts_kernel(ContactArgs 
   double* s_pose = s_pose_all + row * NBMAX * 3;
   const int nb = P.nb;
   const int npairs = nb * (nb - 1) / 2;
-  double dt = P.dt;
+  double dt = DTS ? P.dt_in[scene] : P.dt;                  // per-scene starting dt
+  const bool finished = DTS && dt <= 0.0;                      // the scene has reached its end_t: it stays where it is (one trial, no move)
   int base = 0, trial = 0;
   double maxpen = -1e300;
   bool done = false;
@@ -111,7 +114,7 @@ __global__ void __launch_bounds__(64) lcp_move_find_contacts_kernel(ContactArgs 
     // bodies.py:80-82 (p <- p_start + v dt) and the vertex rotation of bodies.py:211-214
     for (int idx = ll; idx < nb * 3; idx += LPS) {
       double pv = P.p_start[(size_t)scene * nb * 3 + idx];
-      if (P.v) pv += (double)P.v[(size_t)scene * nb * 3 + idx] * dt;
+      if (P.v && !finished) pv += (double)P.v[(size_t)scene * nb * 3 + idx] * dt;
       s_pose[idx] = pv;
     }
     __syncthreads();
@@ -187,7 +190,7 @@ __global__ void __launch_bounds__(64) lcp_move_find_contacts_kernel(ContactArgs 
       ++trial;
       // world.py:95-101
       const bool ok = !(base > 0 && maxpen > P.tol);
-      if (ok || (!P.strict && dt < P.dt_floor) || trial >= P.max_trials || !P.v) done = true;   // (max_trials: the reference would spin)
+      if (ok || (!P.strict && dt < P.dt_floor) || trial >= P.max_trials || !P.v || finished) done = true;   // (max_trials: the reference would spin)
       else dt *= 0.5;
     }
     if (__all(done)) break;
@@ -206,8 +209,8 @@ __global__ void __launch_bounds__(64) lcp_move_find_contacts_kernel(ContactArgs 
   if (ll == 0) {
     P.count[scene] = base;                                  // may exceed maxc: the caller checks
     if (P.max_pen) P.max_pen[scene] = base > 0 ? maxpen : 0.0;
-    if (P.dt_used) P.dt_used[scene] = dt;
-    if (P.t) P.t[scene] += dt;                              // world.py:122
+    if (P.dt_used) P.dt_used[scene] = finished ? 0.0 : dt;
+    if (P.t && !finished) P.t[scene] += dt;                              // world.py:122
     if (P.trials) P.trials[scene] = trial;
   }
 }
@@ -382,7 +385,9 @@ __global__ void __launch_bounds__(64) lcp_joint_jacobian_backward_kernel(int B, 
 //   geo_new = p_geo + [scale v dt_k where it is non-zero or the coordinate is x / y]   cotangent g_g (the reference turns a hull's
 //             vertices by the increment and skips the turn when it is zero: no vertex path through such a step)
 //   rot_new = rot + scale v[body1][0] dt_k  for revolute joints        cotangent g_rot
-// out: g_v = d(loss)/dv (float32).  dt_k > 0 (the step_dt loop stops at dt / 4): the increment is zero exactly where v is.
+// out: g_v = d(loss)/dv (float32).  In a plain step dt_k > 0 (the step_dt loop stops at dt / 4) and the increment is zero exactly where v
+// is.  dt_k = 0 is a scene that had reached its end_t in a sub-step of step(fixed_dt=True) (world.py:72-80): it did not move whatever v
+// is, its g_v is exactly 0 (tot * 0; finite cotangents) and g_p / g_g pass through in the caller.
 // scale = 1 for the dynamics move, 0.5 for the post-stabilisation move (world.py:112).  One thread per scene.
 __global__ void __launch_bounds__(64) lcp_state_update_backward_kernel(int B, int nb, int nj, const double* g_p, const double* g_g,
                                                                        const double* g_rot, const float* v, const double* dt_scene,
@@ -440,9 +445,14 @@ int contact_frame_backward_launch(int B, int nb, int maxc, const int32_t* kind, 
 
 int contacts_launch(const ContactArgs& P, void* stream) {
   if (P.nb > ct::MAXB) return LCP_E_TOOLARGE;
-  if (P.nb <= 6) hipLaunchKernelGGL((ct::lcp_move_find_contacts_kernel<16, 6>), dim3((P.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, P);
-  else if (P.nb <= 16) hipLaunchKernelGGL((ct::lcp_move_find_contacts_kernel<64, 16>), dim3(P.B), dim3(64), 0, (hipStream_t)stream, P);
-  else hipLaunchKernelGGL((ct::lcp_move_find_contacts_kernel<64, ct::MAXB>), dim3(P.B), dim3(64), 0, (hipStream_t)stream, P);   // (15 KB of LDS per scene)
+  if (P.dt_in) {
+    if (P.nb <= 6) hipLaunchKernelGGL((ct::lcp_move_find_contacts_kernel<16, 6, true>), dim3((P.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, P);
+    else if (P.nb <= 16) hipLaunchKernelGGL((ct::lcp_move_find_contacts_kernel<64, 16, true>), dim3(P.B), dim3(64), 0, (hipStream_t)stream, P);
+    else hipLaunchKernelGGL((ct::lcp_move_find_contacts_kernel<64, ct::MAXB, true>), dim3(P.B), dim3(64), 0, (hipStream_t)stream, P);
+  }
+  else if (P.nb <= 6) hipLaunchKernelGGL((ct::lcp_move_find_contacts_kernel<16, 6, false>), dim3((P.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, P);
+  else if (P.nb <= 16) hipLaunchKernelGGL((ct::lcp_move_find_contacts_kernel<64, 16, false>), dim3(P.B), dim3(64), 0, (hipStream_t)stream, P);
+  else hipLaunchKernelGGL((ct::lcp_move_find_contacts_kernel<64, ct::MAXB, false>), dim3(P.B), dim3(64), 0, (hipStream_t)stream, P);   // (15 KB of LDS per scene)
   return hipGetLastError() == hipSuccess ? 0 : LCP_E_LAUNCH;
 }
 

@@ -58,6 +58,8 @@ struct ConstRef {
 // One wavefront per scene, lane = body pair (i < j, lexicographic), the up to 2016 pairs walked 64 at a time; the contacts are
 // compacted in pair order with a wave prefix sum.  Dynamic LDS: 4 arrays over the scene's packed vertex list (V = the host's
 // scene_verts_max): local and rotated vertices, edge normals (V2) and edge lengths, and the owning body of each vertex.
+// DTS: every scene's loop starts from P.dt_in[scene] (compile-time, as in lcp_contacts.hip: the scalar-dt kernel stays the code it was)
+template <bool DTS>
 __global__ void __launch_bounds__(64) lcp_move_find_contacts_wide_kernel(ContactArgs P, int nvcap, int vmax) {
   extern __shared__ double2 s_dyn[];
   V2* s_vloc = reinterpret_cast<V2*>(s_dyn);
@@ -91,7 +93,8 @@ __global__ void __launch_bounds__(64) lcp_move_find_contacts_wide_kernel(Contact
     const double* vl = P.verts_local + ((size_t)scene * nb + b) * nvcap * 2;
     for (int k = ll; k < n; k += 64) { s_vloc[o + k] = v2(vl[2 * k], vl[2 * k + 1]); s_vbody[o + k] = b; }
   }
-  double dt = P.dt;
+  double dt = DTS ? P.dt_in[scene] : P.dt;                  // per-scene starting dt (World.step(fixed_dt=True), world.py:72-80)
+  const bool finished = DTS && dt <= 0.0;                      // the scene has reached its end_t: it stays where it is (one trial, no move)
   int base = 0, trial = 0;
   double maxpen = -1e300;
   bool done = false;
@@ -99,7 +102,7 @@ __global__ void __launch_bounds__(64) lcp_move_find_contacts_wide_kernel(Contact
     // bodies.py:80-82 (p <- p_start + v dt) and the vertex rotation of bodies.py:211-214
     for (int idx = ll; idx < nb * 3; idx += 64) {
       double pv = P.p_start[(size_t)scene * nb * 3 + idx];
-      if (P.v) pv += (double)P.v[(size_t)scene * nb * 3 + idx] * dt;
+      if (P.v && !finished) pv += (double)P.v[(size_t)scene * nb * 3 + idx] * dt;
       s_pose[idx] = pv;
     }
     __syncthreads();
@@ -171,7 +174,7 @@ __global__ void __launch_bounds__(64) lcp_move_find_contacts_wide_kernel(Contact
     ++trial;
     // world.py:95-101
     const bool ok = !(base > 0 && maxpen > P.tol);
-    if (ok || (!P.strict && dt < P.dt_floor) || trial >= P.max_trials || !P.v) done = true;   // (max_trials: the reference would spin)
+    if (ok || (!P.strict && dt < P.dt_floor) || trial >= P.max_trials || !P.v || finished) done = true;   // (max_trials: the reference would spin)
     else dt *= 0.5;
     if (__all(done)) break;
     __syncthreads();
@@ -188,8 +191,8 @@ __global__ void __launch_bounds__(64) lcp_move_find_contacts_wide_kernel(Contact
   if (ll == 0) {
     P.count[scene] = base;                                  // may exceed maxc: the caller checks
     if (P.max_pen) P.max_pen[scene] = base > 0 ? maxpen : 0.0;
-    if (P.dt_used) P.dt_used[scene] = dt;
-    if (P.t) P.t[scene] += dt;                              // world.py:122
+    if (P.dt_used) P.dt_used[scene] = finished ? 0.0 : dt;
+    if (P.t && !finished) P.t[scene] += dt;                              // world.py:122
     if (P.trials) P.trials[scene] = trial;
   }
 }
@@ -337,8 +340,13 @@ int contacts_wide_launch(const ContactArgs& P, int nvcap, int scene_verts_max, v
   if (!ctw::wide_sizes_ok(P.nb, nvcap, scene_verts_max)) return LCP_E_TOOLARGE;
   const int vmax = scene_verts_max < 1 ? 1 : scene_verts_max;
   const size_t lds = ctw::detect_lds(vmax);
-  if (ctw::set_lds(ctw::lcp_move_find_contacts_wide_kernel, lds)) return LCP_E_LAUNCH;
-  hipLaunchKernelGGL(ctw::lcp_move_find_contacts_wide_kernel, dim3(P.B), dim3(64), lds, (hipStream_t)stream, P, nvcap, vmax);
+  if (P.dt_in) {
+    if (ctw::set_lds(ctw::lcp_move_find_contacts_wide_kernel<true>, lds)) return LCP_E_LAUNCH;
+    hipLaunchKernelGGL(ctw::lcp_move_find_contacts_wide_kernel<true>, dim3(P.B), dim3(64), lds, (hipStream_t)stream, P, nvcap, vmax);
+  } else {
+    if (ctw::set_lds(ctw::lcp_move_find_contacts_wide_kernel<false>, lds)) return LCP_E_LAUNCH;
+    hipLaunchKernelGGL(ctw::lcp_move_find_contacts_wide_kernel<false>, dim3(P.B), dim3(64), lds, (hipStream_t)stream, P, nvcap, vmax);
+  }
   return hipGetLastError() == hipSuccess ? 0 : LCP_E_LAUNCH;
 }
 

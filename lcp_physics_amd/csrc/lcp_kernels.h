@@ -135,6 +135,7 @@ struct ContactArgs {
   const double* p_start;                // [B, nb, 3] (rot, x, y)
   const float* v;                       // [B, nb, 3] or NULL (detect at p_start)
   double dt, dt_floor, eps, tol;
+  const double* dt_in;                  // [B] the dt each scene's loop starts from, or NULL = `dt` everywhere; <= 0: the scene is finished
   int strict, max_trials;
   double* p_out;
   float *c_n, *c_p1, *c_p2;
@@ -229,6 +230,10 @@ int contact_frame_backward_launch(int B, int nb, int maxc, const int32_t* kind, 
                                   const int32_t* nverts, const uint8_t* no_contact, const double* p, double eps,
                                   const int32_t* count, const float* g_n, const float* g_p1, const float* g_p2, double* dp,
                                   void* stream);
+// the element-wise kernels around the sub-steps of World.step(fixed_dt=True) (world.py:72-80) - lcp_substep.hip
+int substep_begin_launch(int B, int nb, const double* t, const double* end_t, const float* f, const int32_t* count, double* dt_k,
+                         int32_t* active, int32_t* count_eff, float* f_eff, void* stream);
+int substep_commit_launch(int B, int nb, const int32_t* active, const float* v_old, float* v_new, void* stream);
 // the same for hulls of up to 64 vertices (verts_local[B,nb,nvcap,2], 8 <= nvcap <= 64), up to 64 bodies and
 // CONTACTS_WIDE_MAX_SCENE_VERTS vertices per scene (packed per-scene vertex lists in LDS) - lcp_contacts_wide.hip
 constexpr int CONTACTS_WIDE_MAX_SCENE_VERTS = 1024;

@@ -348,6 +348,47 @@ def solve_dynamics_backward(B, nb, maxc, e, Mdiag, v, f, rest, fric, cb, Je, dt,
     return grads
 
 
+def substep_begin(t, end_t, f, count, out=None):
+    """The head of one sub-step of `World.step(fixed_dt=True)` (`world.py:76-78`) for B scenes, one launch of
+    `lcp_substep_begin_f64`: from the clocks `t`, `end_t` [B] float64, the forces `f` [B,nb,3] float32 and the contact counts
+    `count` [B] int32 -> dict(dt_k [B] float64 = end_t - t where t < end_t else 0, active [B] int32, count_eff [B] int32 = count where
+    active else 0, f_eff [B,nb,3] float32 = float(dt_k) * f).  `out`: such a dict to write into."""
+    lib = _lib.load()
+    for name, x in (("t", t), ("end_t", end_t)):
+        _lib.require_gpu_tensor(x, name, torch.float64)
+    _lib.require_gpu_tensor(f, "f", torch.float32)
+    _lib.require_gpu_tensor(count, "count", torch.int32)
+    B, nb = f.shape[0], f.shape[1]
+    if tuple(f.shape) != (B, nb, 3) or tuple(t.shape) != (B,) or tuple(end_t.shape) != (B,) or tuple(count.shape) != (B,):
+        raise RuntimeError("substep_begin: t, end_t, count must be [B] and f [B,nb,3]")
+    dev = f.device
+    if out is None:
+        out = {"dt_k": torch.empty(B, dtype=torch.float64, device=dev), "active": torch.empty(B, dtype=torch.int32, device=dev),
+               "count_eff": torch.empty(B, dtype=torch.int32, device=dev), "f_eff": torch.empty(B, nb, 3, dtype=torch.float32, device=dev)}
+    P = _lib.ptr
+    with _on_device(dev):
+        rc = lib.lcp_substep_begin_f64(B, nb, P(t), P(end_t), P(f), P(count), P(out["dt_k"]), P(out["active"]), P(out["count_eff"]),
+                                       P(out["f_eff"]), _lib.stream_ptr(dev))
+    _lib.check(rc, "lcp_substep_begin_f64")
+    return out
+
+
+def substep_commit(active, v_old, v_new):
+    """`v_new = active ? v_new : v_old` in place (`lcp_substep_commit_f32`): a scene that has reached its end_t keeps its
+    velocities (`world.py:87` `set_v(new_v)` is never reached for it).  active [B] int32, v_old / v_new [B,nb,3] float32."""
+    lib = _lib.load()
+    _lib.require_gpu_tensor(active, "active", torch.int32)
+    _lib.require_gpu_tensor(v_old, "v_old", torch.float32)
+    _lib.require_gpu_tensor(v_new, "v_new", torch.float32)
+    B, nb = v_new.shape[0], v_new.shape[1]
+    if tuple(v_new.shape) != (B, nb, 3) or v_old.shape != v_new.shape or tuple(active.shape) != (B,):
+        raise RuntimeError("substep_commit: active must be [B], v_old and v_new [B,nb,3]")
+    with _on_device(v_new.device):
+        rc = lib.lcp_substep_commit_f32(B, nb, _lib.ptr(active), _lib.ptr(v_old), _lib.ptr(v_new), _lib.stream_ptr(v_new.device))
+    _lib.check(rc, "lcp_substep_commit_f32")
+    return v_new
+
+
 class _ValueOf(torch.autograd.Function):
     """y = `value` (bitwise: a copy of what the kernel computed) with the gradient of `lin`, the torch expression of the same
     quantity.  `lin + (value - lin).detach()` can differ from `value` by an ulp - and the contact list of the next step was
@@ -622,6 +663,8 @@ class ContactWorld:
     3 nb <= 32, maxc <= 16, e <= 4 run on the four-scenes-per-wave solver, up to 64 contacts and 24 equality rows (3 nb + e <= 56) on the wave-per-scene body-space solver (both with a fused backward),
     anything else on the generic kernels; a differentiable step of such a size goes through the dense boundary
     (physics/dense_step.py: torch assembly on the device + `LCPFunction`, the reference's own route).
+    `step(fixed_dt=True)` is the reference's fixed-interval mode (world.py:72-80): every scene repeats `step_dt(end_t - t)` until
+    its clock reaches `t + dt`, so a roll-out of N steps leaves EVERY scene at `N dt` however often the penetration test halved.
     `post_stab=True` (off by default, as in the reference: utils.py:30) adds the two launches of world.py:109-121 to a
     step: `lcp_post_stabilization_f32` (frictionless LCP + correction move) and a contact re-detection.
     """
@@ -638,7 +681,7 @@ class ContactWorld:
         self.force_fn = force_fn
         self._ps_out = self._ps_ws = None
         self._Je_spare = None
-        self._phase, self._graphs = 0, {}
+        self._phase, self._graphs, self._graphs_fixed = 0, {}, {}
         self._contacts_mod = _contacts
         self.geom = geom
         dev = p.device
@@ -666,6 +709,12 @@ class ContactWorld:
         self.maxc, self.max_iter, self.compute = int(maxc), int(max_iter), compute
         self.solver_eps, self.lim, self.max_trials = solver_eps, not_improved_lim, max_trials
         self.t = torch.zeros(self.B, dtype=torch.float64, device=dev)
+        # fixed-interval stepping (world.py:72-80): scenes that a `step(fixed_dt=True, max_substeps=K)` left short of their end_t (OR over
+        # the steps, device side - `assert_on_schedule()`), and the sub-steps every scene took in the last fixed-interval step
+        self.behind = torch.zeros(self.B, dtype=torch.bool, device=dev)
+        self.substeps = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        self._end_t = torch.zeros(self.B, dtype=torch.float64, device=dev)
+        self._sub = None
         self._xy_mask = (torch.arange(3, device=dev) > 0).reshape(1, 1, 3)    # (rot, x, y): the translation columns (device op: capturable)
         self._ws = self._out = None
         self.check = bool(check)
@@ -688,9 +737,10 @@ class ContactWorld:
         self.p = own(p, torch.float64)
         self.v = torch.zeros(self.B, self.nb, 3, dtype=torch.float32, device=self.p.device) if v is None else own(v, torch.float32)
         self.t.fill_(float(t))
+        self.behind.zero_()
         self.sticky_status.zero_()              # (a device op: an overflow of an earlier roll-out must not fail this one's check)
         self._p_geom_src = self._jrot_src = None
-        self._graphs, self._phase = {}, 0
+        self._graphs, self._graphs_fixed, self._phase = {}, {}, 0
         pd = self.p.detach()
         if self.joints is not None:
             self.joints.jrot1.copy_(self._jrot0 if jrot1 is None else jrot1)
@@ -717,11 +767,27 @@ class ContactWorld:
                                "contact lists were truncated - rebuild the world with a larger maxc"
                                % (bad.numel(), self.maxc, int(bad[0])))
 
-    def run(self, nsteps, graph=True):
+    def assert_on_schedule(self):
+        """Host check (synchronises): no `step(fixed_dt=True, max_substeps=K)` ended with a scene short of its end_t
+        (the reference's loop, world.py:76-78, has no bound; K sub-steps were not enough for the scenes named)."""
+        bad = torch.nonzero(self.behind).flatten()
+        if bad.numel():
+            raise RuntimeError("%d scene(s) did not reach t + dt within max_substeps (scenes %s%s): step with a larger max_substeps"
+                               % (bad.numel(), bad[:8].tolist(), " ..." if bad.numel() > 8 else ""))
+
+    def run(self, nsteps, graph=True, fixed_dt=False, max_substeps=None):
         """`nsteps` calls of `step()`.  With `graph=True` the launches of TWO consecutive steps (after two steps the
         double-buffered state tensors are back in their slots) are captured once into a HIP graph and replayed: the
         host then issues one graph launch per two simulation steps instead of 2-4 kernel launches with their Python
-        marshalling per step - what bounds small batches.  Same kernels, same order, same results."""
+        marshalling per step - what bounds small batches.  Same kernels, same order, same results.
+        `fixed_dt` / `max_substeps`: as in `step()`; a graph needs a launch sequence that does not depend on the data, so `graph=True`
+        with `fixed_dt` requires `max_substeps` (`behind` is checked once at the end)."""
+        if fixed_dt and graph and max_substeps is None:
+            raise ValueError("run(graph=True, fixed_dt=True) needs max_substeps: the synchronising loop cannot be captured")
+        if not fixed_dt and max_substeps is not None:
+            raise ValueError("max_substeps belongs to fixed_dt=True")
+        if fixed_dt:
+            return self._run_fixed(nsteps, graph, max_substeps)
         k = 0
         if graph and nsteps >= 2:
             while not self._graphs and k < 2:
@@ -744,7 +810,36 @@ class ContactWorld:
         if self.check:
             self.assert_not_truncated()                                    # one synchronisation per run, none per step
 
-    def step_autograd(self):
+    def _run_fixed(self, nsteps, graph, max_substeps):
+        """`run()` in the fixed-interval mode.  The graphs of this mode (two steps of `max_substeps` sub-steps each) are kept apart
+        from the plain ones (`_graphs_fixed`): keyed on the buffer parity AND the sub-step count."""
+        step = lambda: self.step(fixed_dt=True, max_substeps=max_substeps)
+        k = 0
+        if graph and nsteps >= 2:
+            key = (self._phase, int(max_substeps))                # (two steps flip the buffers an even number of times)
+            g = self._graphs_fixed.get(key)
+            while g is None and k < 2:
+                step()                                                     # warm-up: every buffer exists before capture
+                k += 1
+            if g is None and nsteps - k >= 2:
+                torch.cuda.synchronize(self.p.device)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    step()
+                    step()
+                self._graphs_fixed[key] = g                                      # (capture only records: nothing has run)
+            while g is not None and nsteps - k >= 2:
+                g.replay()
+                k += 2
+        while k < nsteps:
+            step()
+            k += 1
+        if self.check:
+            self.assert_not_truncated()                                    # one synchronisation per run, none per step
+            if max_substeps is not None:
+                self.assert_on_schedule()
+
+    def step_autograd(self, _end_t=None):
         """`step()` as a node of torch's autograd graph, for losses evaluated after a roll-out (`demos/grad_demo.py:45-50`,
         `experiments/inference.py:55-61`).  Same two launches; the graph of one step is
 
@@ -755,7 +850,9 @@ class ContactWorld:
         `Mdiag, f, rest, fric, v, p` (and what `force_fn` closes over) may require grad.  State tensors are replaced, not
         overwritten, and every step keeps its own workspace and contact snapshot for the backward.  The joint Jacobian of
         revolute / fixed joints is differentiated through the pose and the joint angle (dL/dJe: lcp_step_backward_je_f32);
-        with `post_stab` the correction move is one more node (`PostStabilizationFunction`, world.py:109-121)."""
+        with `post_stab` the correction move is one more node (`PostStabilizationFunction`, world.py:109-121).
+        `_end_t` (from `step(differentiable=True, fixed_dt=True)`): this is ONE sub-step `step_dt(end_t - t)` of world.py:76-78 - dt_k is a
+        constant of the graph (a Python float in the reference), a scene at its end_t passes state and gradient through unchanged."""
         ct = self._contacts_mod
         # the contact buffers at the current pose become this step's frame (kept for its backward); the detection below fills a
         # fresh set - no copies
@@ -765,7 +862,7 @@ class ContactWorld:
         self._autograd_owned = True
         # HIP graphs captured by an earlier run(graph=True) hold raw pointers to the buffers retired here (they now belong to this
         # step's backward) and to the old state tensors: a later run() must capture again on the new ones
-        self._graphs, self._phase = {}, 0
+        self._graphs, self._graphs_fixed, self._phase = {}, {}, 0
         # the pose the GEOMETRY is differentiated at: the same values as self.p, but a rotation increment that is exactly
         # zero carries no gradient - the reference turns its hulls' vertices by the increment and skips the turn when the
         # increment is zero (bodies.py:199-202 `if rot.item() != 0: self.rotate_verts(rot)`), so its autograd has no
@@ -777,6 +874,14 @@ class ContactWorld:
         shape_in = shape_in if any(t is not None for t in shape_in) else ()
         c_n, c_p1, c_p2 = ct.ContactFrameFunction.apply(p_geo, self.geom, frame, self.eps, *shape_in)
         f = self.f if self.force_fn is None else self.force_fn(self.t).to(torch.float32).contiguous()
+        count, dt_solve, sub = frame.count, self.dt, None
+        if _end_t is not None:
+            # u = M v + dt_k f(t) (engines.py:31-32) as the solve with dt = 1 and f_eff = float(dt_k) * f: the same fp32 value, and the
+            # solve's df chains through the product; a finished scene (dt_k = 0) takes the no-contact branch
+            sub = substep_begin(self.t, _end_t, f.detach(), frame.count)
+            active = sub["active"].bool().reshape(-1, 1, 1)
+            f = sub["dt_k"].to(torch.float32).reshape(-1, 1, 1) * f
+            count, dt_solve = sub["count_eff"], 1.0
         opts = {"max_iter": self.max_iter, "eps": self.solver_eps, "not_improved_lim": self.lim, "compute": self.compute,
                 "pinned": self._pinned}
         Je = self.Je
@@ -788,12 +893,16 @@ class ContactWorld:
                 self._jrot_ad, self._jrot_src = js.jrot1.clone(), self.p
             Je = _JointJacobianFn.apply(self.p, self._jrot_ad, js.jr1, js, self.Je)
         v_new = SolveDynamicsFunction.apply(self.Mdiag, self.v.contiguous(), f, self.rest, self.fric, c_n, c_p1, c_p2, frame.c_i1,
-                                            frame.c_i2, frame.count, Je, self.dt, opts)
+                                            frame.c_i2, count, Je, dt_solve, opts)
+        if sub is not None:                                                # world.py:87 set_v(new_v): not for a scene that is finished
+            v_new = torch.where(active, v_new, self.v)
+            self.substeps += sub["active"]
         out = opts["last"]
         torch.bitwise_or(self.sticky_status, out["status"], out=self.sticky_status)
         p_start = self.p
         ct.move_and_find_contacts(self.geom, p_start.detach(), v_new.detach(), self.dt, eps=self.eps, tol=self.tol,
-                                  strict=self.strict, dt_floor=self.dt / 4, max_trials=self.max_trials, t=self.t, out=cb)
+                                  strict=self.strict, dt_floor=self.dt / 4, max_trials=self.max_trials, t=self.t, out=cb,
+                                  dt_scene=None if sub is None else sub["dt_k"])
         # the accepted pose: the kernel's value, the gradient of p + v dt_used (a zero rotation increment carries no gradient to the geometry)
         self.v = v_new
         if js is not None:                                                 # joint.move(dt): rot1 += body1.v[0] dt (constraints.py:39-43)
@@ -837,29 +946,82 @@ class ContactWorld:
         ret["v_new"] = v_new
         return ret
 
-    def step(self, differentiable=False):
-        """`World.step()` = `step_dt(self.dt)` (`world.py:72-122`) for every scene."""
+    def step(self, differentiable=False, fixed_dt=False, max_substeps=None):
+        """`World.step()` = `step_dt(self.dt)` (`world.py:72-122`) for every scene.
+        `fixed_dt=True`: `World.step(fixed_dt=True)` (`world.py:72-80`) - every scene repeats `step_dt(end_t - t)` until its clock
+        reaches `end_t = t + dt`.  Every sub-step launches the whole batch; a scene that is finished keeps `p`, `v`, `t`, joint angles and
+        contact records.  `max_substeps=None`: until no scene is active (one host synchronisation per sub-step; RuntimeError after 64 -
+        the reference would spin).  `max_substeps=K`: exactly K sub-steps and no synchronisation (capturable); scenes still short of
+        `end_t` are OR-ed into `self.behind` (`assert_on_schedule()`).  `self.substeps` [B]: the sub-steps each scene took."""
+        if fixed_dt:
+            return self._step_fixed(differentiable, max_substeps)
+        if max_substeps is not None:
+            raise ValueError("max_substeps belongs to fixed_dt=True")
         if differentiable:
             return self.step_autograd()
+        return self._advance()
+
+    MAX_SUBSTEPS = 64                    # where the synchronising loop of `step(fixed_dt=True)` gives up (the role of `max_trials`)
+
+    def _step_fixed(self, differentiable, max_substeps):
+        """world.py:72-80 for every scene."""
+        _lib.require_gpu_tensor(self.t, "t", torch.float64)               # (no CPU route)
+        if max_substeps is not None and int(max_substeps) < 1:
+            raise ValueError("max_substeps must be at least 1")
+        if differentiable:
+            end_t = self.t + self.dt                                       # world.py:75 (this step's own tensor: its graph keeps it)
+        else:
+            end_t = torch.add(self.t, self.dt, out=self._end_t)
+        self.substeps.zero_()
+        k = 0
+        while True:
+            if max_substeps is None:
+                if k >= self.MAX_SUBSTEPS:
+                    late = torch.nonzero(self.t < end_t).flatten()
+                    raise RuntimeError("step(fixed_dt=True): %d scene(s) have not reached t + dt after %d sub-steps (scenes %s%s)"
+                                       % (late.numel(), k, late[:8].tolist(), " ..." if late.numel() > 8 else ""))
+            elif k >= int(max_substeps):
+                break
+            ret = self.step_autograd(_end_t=end_t) if differentiable else self._advance(fixed=True)
+            k += 1
+            if max_substeps is None and not bool((self.t < end_t).any()):  # world.py:76 (the one synchronisation of a sub-step)
+                break
+        if max_substeps is not None:
+            torch.bitwise_or(self.behind, self.t < end_t, out=self.behind)
+        ret["substeps"] = self.substeps
+        return ret
+
+    def _advance(self, fixed=False):
+        """`step_dt` (`world.py:83-122`) for every scene: with dt = `self.dt`, or (`fixed`) with `self._end_t - t` per scene."""
         if getattr(self, "_autograd_owned", False):
             # the state tensors are outputs of the autograd graph (their storage belongs to the retired contact buffers of the last
             # differentiable step): the double buffering below must not hand them to a kernel as an output slot
             # - and the contact buffers of the last differentiable step (dt_used, the accepted pose) are saved in that graph
             self.p, self.v, self._autograd_owned = self.p.detach().clone(), self.v.detach().clone(), False
             self.contacts = self.contacts.clone()
-            self._graphs, self._phase = {}, 0                            # (no graph captured before these buffers existed may replay)
-        self._phase ^= 1
+            self._graphs, self._graphs_fixed, self._phase = {}, {}, 0                            # (no graph captured before these buffers existed may replay)
+        self._phase ^= 1                                                 # (the parity of the double buffers: one flip per swap below)
         cb = self.contacts
         f = self.f if self.force_fn is None else self.force_fn(self.t).to(torch.float32).contiguous()
-        out = solve_dynamics(self.B, self.nb, self.maxc, self.e, cb.count, self.Mdiag, self.v, f, self.rest,
-                             self.fric, cb, self.Je, self.dt, eps=self.solver_eps, not_improved_lim=self.lim,
+        count, dt_solve, sub = cb.count, self.dt, None
+        if fixed:
+            # dt_k = end_t - t per scene (0: finished); the solve forms u = M v + dt_k f as M v + 1 * fl(float(dt_k) f) - the same fp32
+            # value - and a finished scene takes its no-contact branch
+            sub = self._sub = substep_begin(self.t, self._end_t, f, cb.count, out=self._sub)
+            f, count, dt_solve = sub["f_eff"], sub["count_eff"], 1.0
+        out = solve_dynamics(self.B, self.nb, self.maxc, self.e, count, self.Mdiag, self.v, f, self.rest,
+                             self.fric, cb, self.Je, dt_solve, eps=self.solver_eps, not_improved_lim=self.lim,
                              max_iter=self.max_iter, compute=self.compute, ws=self._ws, out=self._out, pinned=self._pinned)
         self._ws, self._out = out["ws"], out
         torch.bitwise_or(self.sticky_status, out["status"], out=self.sticky_status)
         self.v, out["v_new"] = out["v_new"], self.v                      # world.py:87 set_v(new_v)
+        if fixed:
+            substep_commit(sub["active"], out["v_new"], self.v)          # ... which a finished scene does not reach
+            self.substeps += sub["active"]
         self._contacts_mod.move_and_find_contacts(self.geom, self.p, self.v, self.dt, eps=self.eps, tol=self.tol,
                                                   strict=self.strict, dt_floor=self.dt / 4,
-                                                  max_trials=self.max_trials, t=self.t, out=cb)
+                                                  max_trials=self.max_trials, t=self.t, out=cb,
+                                                  dt_scene=sub["dt_k"] if fixed else None)
         self.p, cb.p_out = cb.p_out, self.p                              # accepted pose becomes the state (double buffer)
         if self.joints is not None:                                      # joint.move(dt) + the Jacobian at the new pose (world.py:91-92)
             self._Je_spare = self.joints.jacobian(self.p, v=self.v, dt_scene=cb.dt_used, out=self._Je_spare)

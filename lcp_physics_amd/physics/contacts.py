@@ -172,10 +172,13 @@ class ContactBuffers:
 
 
 def move_and_find_contacts(geom, p_start, v, dt, maxc=16, eps=EPSILON, tol=TOL, strict=True, dt_floor=None,
-                           max_trials=64, t=None, out=None):
+                           max_trials=64, t=None, out=None, dt_scene=None):
     """`p <- p_start + v dt`, contacts at the new pose, dt halving while a contact penetrates by more than `tol`
     (`world.py:88-101`) for every scene.  `v=None` detects at `p_start` (the `find_contacts()` of
-    `World.__init__`, `world.py:65-66`).  Returns the `ContactBuffers` (p_out = accepted pose)."""
+    `World.__init__`, `world.py:65-66`).  Returns the `ContactBuffers` (p_out = accepted pose).
+    `dt_scene` [B] float64: every scene's loop starts from its own dt (`lcp_move_find_contacts_dts_f64`: the sub-steps of
+    `World.step(fixed_dt=True)`, `world.py:72-80`); a scene with dt_scene <= 0 stays at `p_start` with dt_used = 0.  `dt` then only
+    sets the default `dt_floor`."""
     lib = _lib.load()
     B, nb = geom.B, geom.nb
     _lib.require_gpu_tensor(geom.kind, "kind", torch.int32)
@@ -200,7 +203,17 @@ def move_and_find_contacts(geom, p_start, v, dt, maxc=16, eps=EPSILON, tol=TOL, 
             P(p_start), P(v), float(dt), float(dt / 4 if dt_floor is None else dt_floor), int(bool(strict)),
             int(max_trials), float(eps), float(tol), P(out.p_out), P(out.c_n), P(out.c_p1), P(out.c_p2),
             P(out.c_pen), P(out.c_i1), P(out.c_i2), P(out.count), P(out.max_pen), P(out.dt_used), P(t),
-            P(out.trials), _lib.stream_ptr(dev))
+            P(out.trials))
+    if dt_scene is not None:
+        _lib.require_gpu_tensor(dt_scene, "dt_scene", torch.float64)
+        if tuple(dt_scene.shape) != (B,):
+            raise RuntimeError("dt_scene must be [B]")
+        with torch.cuda.device(dev):
+            rc = lib.lcp_move_find_contacts_dts_f64(B, nb, out.maxc, geom.nvcap, 0 if not geom.wide else geom.verts_max(), *args,
+                                                    P(dt_scene), _lib.stream_ptr(dev))
+        _lib.check(rc, "lcp_move_find_contacts_dts_f64")
+        return out
+    args += (_lib.stream_ptr(dev),)
     if geom.wide:
         with torch.cuda.device(dev):
             rc = lib.lcp_move_find_contacts_nv_f64(B, nb, out.maxc, geom.nvcap, geom.verts_max(), *args)
