@@ -487,6 +487,46 @@ int lcp_contact_frame_backward_shape_f64(int B, int nb, int maxc, int nvcap, int
                                          const float* g_n, const float* g_p1, const float* g_p2,
                                          double* d_radius, double* d_verts_local, void* stream);
 
+/* ---- bodies: mass properties and gravity from shape and mass ----
+ * Per-body status bits of lcp_body_properties_f64.  A hull gets the first that applies of COUNT and DEGENERATE alone (nothing
+ * else can be said of it), otherwise ORIENTATION and / or NONCONVEX; a circle only DEGENERATE (non-finite radius or mass). */
+#define LCP_BODY_ST_COUNT        1  /* nverts < 3 or nverts > cap                        (bodies.py:169 `len(verts) > 2`)          */
+#define LCP_BODY_ST_ORIENTATION  2  /* sum (x2 - x1)(y2 + y1) >= 0: not the reference's vertex order (bodies.py:228-235)            */
+#define LCP_BODY_ST_NONCONVEX    4  /* two consecutive edges turn against the polygon's orientation                               */
+#define LCP_BODY_ST_DEGENERATE   8  /* sum cross_2d(v_i+1, v_i) == 0 (no area), or a non-finite vertex, radius or mass            */
+
+/* What the reference's body constructors compute, for B x nb bodies in one launch (lcp_bodies.hip): Circle.__init__ /
+ * _get_ang_inertia (physics/bodies.py:116-126), Hull.__init__ (bodies.py:162-177: `_get_centroid` :216-226, the recentred
+ * `verts` :171, `pos = ref_point + centroid` :173, `_is_clockwise` :228-235), Hull._get_ang_inertia (:179-189, on the recentred
+ * vertices), Body.M (:44-47) and Gravity.set_body (forces.py:64-67).  A Rect is the hull of its four vertices (bodies.py:260-262).
+ *   in (all required): kind[B,nb] i32 (0 circle, otherwise hull), radius[B,nb] f64 (circles), verts_raw[B,nb,cap,2] f64 relative
+ *       to the body's reference point in the reference's vertex order (slots >= nverts are never read), nverts[B,nb] i32
+ *       (hulls), mass[B,nb] f64; g: the gravity constant.  8 <= cap <= 64, else LCP_E_BADARG; B or nb of 0: success, no launch.
+ *   out (each optional, NULL = skipped, at least one; written, never accumulated):
+ *       centroid[B,nb,2] f64 (circle: 0), verts_local[B,nb,cap,2] f64 = verts_raw - centroid (slots >= nverts and circles: 0),
+ *       inertia[B,nb] f64, Mdiag[B,nb,3] f32 = (I, m, m), f_gravity[B,nb,3] f32 = (0, 0, m g), status[B,nb] i32 (LCP_BODY_ST_*).
+ * A flagged body still has every output written (possibly NaN); nothing is read beyond min(nverts, cap) vertices.
+ * fp64 arithmetic; cap rounded up to a power of two lanes per body (8 bodies per wavefront at cap 8), sums by cross-lane
+ * butterflies: the result of a body depends on its own inputs and cap only, not on its place in the batch. */
+int lcp_body_properties_f64(int B, int nb, int cap, const int32_t* kind, const double* radius, const double* verts_raw,
+                            const int32_t* nverts, const double* mass, double g,
+                            double* centroid, double* verts_local, double* inertia, float* Mdiag, float* f_gravity,
+                            int32_t* status, void* stream);
+
+/* Backward of lcp_body_properties_f64: what the reference's autograd gives the raw vertices handed to Hull (through the centroid
+ * bodies.py:216-226, the recentred vertices :171 and the inertia :179-189), Circle.rad (:125-126) and the mass (:44-47,
+ * forces.py:67).  Same raw inputs (all required), centroid and recentred vertices are recomputed: no saved state.
+ *   cotangents in (each optional, NULL = zero): g_centroid[B,nb,2] f64, g_verts_local[B,nb,cap,2] f64 (slots >= nverts are not
+ *       read), g_inertia[B,nb] f64, g_Mdiag[B,nb,3] f32, g_f[B,nb,3] f32.
+ *   out (each optional, at least one; written, never accumulated): g_verts_raw[B,nb,cap,2] f64 (slots >= nverts and circles:
+ *       0), g_radius[B,nb] f64 (hulls: 0), g_mass[B,nb] f64.
+ * |cross| differentiates to its sign.  Same sizes, mapping and error codes as the forward. */
+int lcp_body_properties_backward_f64(int B, int nb, int cap, const int32_t* kind, const double* radius, const double* verts_raw,
+                                     const int32_t* nverts, const double* mass, double g,
+                                     const double* g_centroid, const double* g_verts_local, const double* g_inertia,
+                                     const float* g_Mdiag, const float* g_f,
+                                     double* g_verts_raw, double* g_radius, double* g_mass, void* stream);
+
 /* ---- debugging / A-B aids (not part of the drop-in surface) ----
  * lcp_debug_set_trace: when non-NULL, the dense forward writes trace[B, max_iter, 4] =
  *   (resid, mu, sigma, alpha) per PDIPM iteration (device pointer to doubles).

@@ -31,6 +31,11 @@ ST_SINGULAR_T = 4
 ST_NAN = 8
 ST_TRUNCATED = 16
 
+BODY_ST_COUNT = 1
+BODY_ST_ORIENTATION = 2
+BODY_ST_NONCONVEX = 4
+BODY_ST_DEGENERATE = 8
+
 _ERRORS = {-1: "LCP_E_BADARG", -2: "LCP_E_TOOLARGE", -3: "LCP_E_LAUNCH"}
 
 _c = ctypes
@@ -69,6 +74,8 @@ SIGNATURES = {
     "lcp_substep_commit_f32": (_I, [_I] * 2 + [_P] * 3 + [_P]),
     "lcp_contact_frame_backward_nv_f64": (_I, [_I] * 5 + [_P] * 6 + [_c.c_double] + [_P] * 7 + [_P]),
     "lcp_contact_frame_backward_shape_f64": (_I, [_I] * 5 + [_P] * 5 + [_c.c_double] + [_P] * 8 + [_P]),
+    "lcp_body_properties_f64": (_I, [_I] * 3 + [_P] * 5 + [_c.c_double] + [_P] * 6 + [_P]),
+    "lcp_body_properties_backward_f64": (_I, [_I] * 3 + [_P] * 5 + [_c.c_double] + [_P] * 5 + [_P] * 3 + [_P]),
     "lcp_joint_jacobian_backward_f64": (_I, [_I] * 4 + [_P] * 6 + [_P, _P, _P]),
     "lcp_state_update_backward_f64": (_I, [_I] * 3 + [_P] * 5 + [_c.c_double] + [_P] * 3 + [_P]),
     "lcp_debug_set_trace": (None, [_P]),

@@ -659,4 +659,27 @@ int lcp_contact_frame_backward_shape_f64(int B, int nb, int maxc, int nvcap, int
                                                   c_i1, c_i2, g_n, g_p1, g_p2, d_radius, d_verts_local, stream);
 }
 
+int lcp_body_properties_f64(int B, int nb, int cap, const int32_t* kind, const double* radius, const double* verts_raw,
+                            const int32_t* nverts, const double* mass, double g, double* centroid, double* verts_local,
+                            double* inertia, float* Mdiag, float* f_gravity, int32_t* status, void* stream) {
+  if (B < 0 || nb < 0 || cap < 8 || cap > 64) return LCP_E_BADARG;
+  if (!kind || !radius || !verts_raw || !nverts || !mass) return LCP_E_BADARG;
+  if (!centroid && !verts_local && !inertia && !Mdiag && !f_gravity && !status) return LCP_E_BADARG;   // (nothing asked for)
+  if (B == 0 || nb == 0) return 0;
+  return lcp::body_properties_launch(B, nb, cap, kind, radius, verts_raw, nverts, mass, g, centroid, verts_local, inertia, Mdiag,
+                                     f_gravity, status, stream);
+}
+
+int lcp_body_properties_backward_f64(int B, int nb, int cap, const int32_t* kind, const double* radius, const double* verts_raw,
+                                     const int32_t* nverts, const double* mass, double g, const double* g_centroid,
+                                     const double* g_verts_local, const double* g_inertia, const float* g_Mdiag, const float* g_f,
+                                     double* g_verts_raw, double* g_radius, double* g_mass, void* stream) {
+  if (B < 0 || nb < 0 || cap < 8 || cap > 64) return LCP_E_BADARG;
+  if (!kind || !radius || !verts_raw || !nverts || !mass) return LCP_E_BADARG;
+  if (!g_verts_raw && !g_radius && !g_mass) return LCP_E_BADARG;                                       // (nothing asked for)
+  if (B == 0 || nb == 0) return 0;
+  return lcp::body_properties_backward_launch(B, nb, cap, kind, radius, verts_raw, nverts, mass, g, g_centroid, g_verts_local,
+                                              g_inertia, g_Mdiag, g_f, g_verts_raw, g_radius, g_mass, stream);
+}
+
 }  // extern "C"

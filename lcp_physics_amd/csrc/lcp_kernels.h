@@ -242,6 +242,17 @@ int contact_frame_backward_wide_launch(int B, int nb, int maxc, int nvcap, int s
                                        const double* radius, const double* verts_local, const int32_t* nverts, const double* p,
                                        double eps, const int32_t* count, const int32_t* c_i1, const int32_t* c_i2,
                                        const float* g_n, const float* g_p1, const float* g_p2, double* dp, void* stream);
+// the reference's body constructors (bodies.py:15-290, forces.py:51-67): centroid, recentred vertices, inertia, mass matrix
+// diagonal and gravity from the raw shape and the mass, and their chain rule - lcp_bodies.hip (cap rounded up to a power of two
+// lanes per body, segmented cross-lane sums; sizes checked by the caller: 8 <= cap <= 64)
+int body_properties_launch(int B, int nb, int cap, const int32_t* kind, const double* radius, const double* verts_raw,
+                           const int32_t* nverts, const double* mass, double g, double* centroid, double* verts_local,
+                           double* inertia, float* Mdiag, float* f_gravity, int32_t* status, void* stream);
+int body_properties_backward_launch(int B, int nb, int cap, const int32_t* kind, const double* radius, const double* verts_raw,
+                                    const int32_t* nverts, const double* mass, double g, const double* g_centroid,
+                                    const double* g_verts_local, const double* g_inertia, const float* g_Mdiag, const float* g_f,
+                                    double* g_verts_raw, double* g_radius, double* g_mass, void* stream);
+
 // backward of the contact frame with respect to the SHAPE (radii, body-frame hull vertices) at the same sizes: one lane per
 // (contacting pair, shape coordinate the pair's records were built from) - lcp_contacts_shape.hip
 int contact_frame_backward_shape_launch(int B, int nb, int maxc, int nvcap, int scene_verts_max, const int32_t* kind,

@@ -41,9 +41,11 @@ class GeometryBatch:
     `radius` and `verts_local` may require grad (or carry a graph: one learnable shape expanded over the B scenes, say):
     `ContactWorld.step(differentiable=True)` then back-propagates to them through the contact frame
     (`contact_frame_backward_shape`), as the reference's autograd does to `Circle.rad` / `Hull.verts`.  The kernels read
-    their values only.  What stays the caller's job, as in the reference's `Hull.__init__`: vertices that are convex,
-    counter-clockwise and centred on the centroid - and the dependence of `Mdiag` on the shape (inertia of a disc or a
-    polygon), which is plain torch on the same leaves and composes with the `Mdiag` gradient of the step."""
+    their values only.  A batch built by hand (or by `from_shapes`) takes vertices that are convex, in the reference's order and
+    centred on the centroid, and leaves `Mdiag` to the caller; `physics.bodies.BodyBatch.from_list` does what the reference's
+    `Hull.__init__` does instead - validation, centroid, recentred vertices, position, inertia, mass matrix, gravity from the raw
+    shape and the mass in one launch (`lcp_body_properties_f64`), differentiable - and hands out a `GeometryBatch` whose `radius` and
+    `verts_local` carry that graph."""
     kind: torch.Tensor
     radius: torch.Tensor
     verts_local: torch.Tensor
