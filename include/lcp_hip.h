@@ -438,6 +438,39 @@ int lcp_move_find_contacts_dts_f64(int B, int nb, int maxc, int nvcap, int scene
                                    double* dt_used, double* t, int32_t* trials,
                                    const double* dt_scene, void* stream);
 
+/* Detection with a broadphase in front of the narrow phase (lcp_contacts_bp.hip).  The reference's World.find_contacts
+ * (physics/world.py:139-142) collides its geoms through ODE's HashSpace over bounding spheres padded by the margin
+ * (physics/bodies.py:_create_geom), so only nearby pairs reach the contact handler; the _nv_ / _dts_ entries hand it all
+ * nb (nb - 1) / 2 pairs.  This entry culls at every trial pose first.  Per body b: R_b the bounding radius about its position (the
+ * radius of a circle, max |verts_local| of a hull), box_b the (min, max) of its rotated vertices relative to the position, mitre_b the
+ * (min, max) over its vertices of m_k = (n_{k-1} + n_k) / (1 + n_{k-1} . n_k) with n the outward unit edge normals, kappa_b = max |m_k|
+ * (a circle: box -+ radius, mitre -+ 1, kappa 1).  For the ordered pair (a, b), r = R_b + eps, S = R_a + kappa_a r, d = pos_b - pos_a:
+ *   T(a, b):  |d|^2 <= S^2 (1 + 4e-9)  and  box_a.min + r mitre_a.min - 1e-9 S <= d <= box_a.max + r mitre_a.max + 1e-9 S on both axes.
+ * A pair i < j reaches the narrow phase iff no_contact[i][j] is not set and T(i, j) and T(j, i) hold.  T relaxes the gates of the
+ * narrow phase itself: hull / hull reports a point only after the separation along every edge normal of both hulls is <= eps, which
+ * puts pos_b inside hull a offset outwards by r (vertices v_k + r m_k) - the DISTANCE between two hulls with a record can exceed eps
+ * (two corners: up to eps / sin(angle / 2)), which kappa and the mitres cover; circle / hull and circle / circle report a point
+ * only within eps.  So no record is lost, for convex, counter-clockwise, non-degenerate hulls, and the survivors keep the pair order.
+ * The arguments of lcp_move_find_contacts_dts_f64 in the same order, then
+ *   dt_scene[B]    or NULL.  NULL: every scene starts from the scalar `dt` (lcp_move_find_contacts_nv_f64); otherwise the
+ *                  per-scene dt and the finished scenes of lcp_move_find_contacts_dts_f64.
+ *   candidates[B]  or NULL: the number of pairs that passed the cull at the accepted trial pose (p_out).
+ * Sizes and errors are those of the _nv_ entry, checked before any launch: nb <= 64, 8 <= nvcap <= 64, scene_verts_max <= 1024
+ * (LCP_E_TOOLARGE beyond) - one kernel for all of them, nb <= 32 at capacity 8 included, so scene_verts_max is always read.
+ * A scene whose vertices exceed scene_verts_max gets count = -1, padded records and candidates = 0.
+ * Contract: every other output is bitwise that of lcp_move_find_contacts_nv_f64 (dt_scene NULL) / lcp_move_find_contacts_dts_f64
+ * on the same inputs. */
+int lcp_move_find_contacts_bp_f64(int B, int nb, int maxc, int nvcap, int scene_verts_max,
+                                  const int32_t* kind, const double* radius, const double* verts_local,
+                                  const int32_t* nverts, const uint8_t* no_contact,
+                                  const double* p_start, const float* v,
+                                  double dt, double dt_floor, int strict, int max_trials,
+                                  double eps, double tol,
+                                  double* p_out, float* c_n, float* c_p1, float* c_p2, double* c_pen,
+                                  int32_t* c_i1, int32_t* c_i2, int32_t* count, double* max_pen,
+                                  double* dt_used, double* t, int32_t* trials,
+                                  const double* dt_scene, int32_t* candidates, void* stream);
+
 /* The head of one sub-step of World.step(fixed_dt=True) (physics/world.py:76-78) for B scenes, element-wise:
  *   in : t[B], end_t[B] float64 (the scenes' clocks and the time their step ends at)  f[B,nb,3] float32 (the forces at t)
  *        count[B] (the contacts of the current pose)

@@ -70,6 +70,8 @@ SIGNATURES = {
                                                              _c.c_double] + [_P] * 12 + [_P]),
     "lcp_move_find_contacts_dts_f64": (_I, [_I] * 5 + [_P] * 7 + [_c.c_double, _c.c_double, _I, _I, _c.c_double,
                                                               _c.c_double] + [_P] * 12 + [_P, _P]),
+    "lcp_move_find_contacts_bp_f64": (_I, [_I] * 5 + [_P] * 7 + [_c.c_double, _c.c_double, _I, _I, _c.c_double,
+                                                             _c.c_double] + [_P] * 12 + [_P, _P, _P]),
     "lcp_substep_begin_f64": (_I, [_I] * 2 + [_P] * 8 + [_P]),
     "lcp_substep_commit_f32": (_I, [_I] * 2 + [_P] * 3 + [_P]),
     "lcp_contact_frame_backward_nv_f64": (_I, [_I] * 5 + [_P] * 6 + [_c.c_double] + [_P] * 7 + [_P]),

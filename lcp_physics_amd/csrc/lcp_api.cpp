@@ -623,6 +623,28 @@ int lcp_move_find_contacts_dts_f64(int B, int nb, int maxc, int nvcap, int scene
   return lcp::contacts_wide_launch(P, nvcap, scene_verts_max, stream);
 }
 
+// the same loop with a broadphase in front of the narrow phase (lcp_contacts_bp.hip); dt_scene NULL: the scalar dt
+int lcp_move_find_contacts_bp_f64(int B, int nb, int maxc, int nvcap, int scene_verts_max, const int32_t* kind, const double* radius,
+                                  const double* verts_local, const int32_t* nverts, const uint8_t* no_contact,
+                                  const double* p_start, const float* v, double dt, double dt_floor, int strict,
+                                  int max_trials, double eps, double tol, double* p_out, float* c_n, float* c_p1,
+                                  float* c_p2, double* c_pen, int32_t* c_i1, int32_t* c_i2, int32_t* count,
+                                  double* max_pen, double* dt_used, double* t, int32_t* trials, const double* dt_scene,
+                                  int32_t* candidates, void* stream) {
+  if (B <= 0 || nb <= 0 || maxc <= 0 || max_trials <= 0 || scene_verts_max < 0) return LCP_E_BADARG;
+  if (!kind || !radius || !verts_local || !nverts || !p_start) return LCP_E_BADARG;
+  if (!c_n || !c_p1 || !c_p2 || !c_i1 || !c_i2 || !count) return LCP_E_BADARG;
+  lcp::ContactArgs P;
+  memset(&P, 0, sizeof(P));
+  P.B = B; P.nb = nb; P.maxc = maxc; P.kind = kind; P.nverts = nverts; P.radius = radius;
+  P.verts_local = verts_local; P.no_contact = no_contact; P.p_start = p_start; P.v = v;
+  P.dt = dt; P.dt_floor = dt_floor; P.eps = eps; P.tol = tol; P.strict = strict; P.max_trials = max_trials;
+  P.p_out = p_out; P.c_n = c_n; P.c_p1 = c_p1; P.c_p2 = c_p2; P.c_pen = c_pen; P.c_i1 = c_i1; P.c_i2 = c_i2;
+  P.count = count; P.max_pen = max_pen; P.dt_used = dt_used; P.t = t; P.trials = trials;
+  P.dt_in = dt_scene;
+  return lcp::contacts_bp_launch(P, nvcap, scene_verts_max, candidates, stream);     // (checks the sizes before it launches)
+}
+
 // the bookkeeping of world.py:72-80 around one sub-step (lcp_substep.hip)
 int lcp_substep_begin_f64(int B, int nb, const double* t, const double* end_t, const float* f, const int32_t* count, double* dt_k,
                           int32_t* active, int32_t* count_eff, float* f_eff, void* stream) {

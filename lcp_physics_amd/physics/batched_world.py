@@ -667,11 +667,13 @@ class ContactWorld:
     its clock reaches `t + dt`, so a roll-out of N steps leaves EVERY scene at `N dt` however often the penetration test halved.
     `post_stab=True` (off by default, as in the reference: utils.py:30) adds the two launches of world.py:109-121 to a
     step: `lcp_post_stabilization_f32` (frictionless LCP + correction move) and a contact re-detection.
+    `broadphase=True` (off by default) runs every detection on `lcp_move_find_contacts_bp_f64` (lcp_contacts_bp.hip): the body pairs are
+    culled by bounding circle and box before the narrow phase, the records are the same bit for bit, `candidates` [B] counts the survivors.
     """
 
     def __init__(self, geom, p, v, Mdiag, f, rest, fric, Je=None, dt=1.0 / 30, eps=0.1, tol=1e-6,
                  strict_no_penetration=True, maxc=16, max_iter=10, compute="f64", solver_eps=1e-12,
-                 not_improved_lim=3, max_trials=64, check=True, post_stab=False, force_fn=None, joints=None):
+                 not_improved_lim=3, max_trials=64, check=True, post_stab=False, force_fn=None, joints=None, broadphase=False):
         from . import contacts as _contacts
         self.post_stab = bool(post_stab)
         # `force_fn(t) -> f [B,nb,3] float32` replaces the constant force: the batched form of the reference's
@@ -721,8 +723,14 @@ class ContactWorld:
         # OR of every step's per-scene status bits (device side, no synchronisation): LCP_ST_TRUNCATED in here means a
         # scene once had more contacts than `maxc` and was solved with a cut list - `assert_not_truncated()` / `run()`
         self.sticky_status = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        # `broadphase=True`: every detection of this world culls the body pairs by bounding circle and box before the narrow phase
+        # (`lcp_move_find_contacts_bp_f64`: the role of the reference's ODE space, world.py:139-142) - the same records bit for bit;
+        # `candidates` [B] int32 then holds the pairs that passed the cull in the latest detection
+        self.broadphase = bool(broadphase)
+        self.candidates = torch.zeros(self.B, dtype=torch.int32, device=dev) if self.broadphase else None
+        self._bp = {"broadphase": True, "candidates": self.candidates} if self.broadphase else {}
         # world.py:65-66: contacts of the initial pose; :67-70: refuse interpenetration at start
-        self.contacts = _contacts.find_contacts(geom, self.p, maxc=self.maxc, eps=self.eps)
+        self.contacts = _contacts.find_contacts(geom, self.p, maxc=self.maxc, eps=self.eps, **self._bp)
         if check:
             self.check_capacity()
             if self.strict and bool((self.contacts.max_pen > self.tol).any()):
@@ -745,7 +753,7 @@ class ContactWorld:
         if self.joints is not None:
             self.joints.jrot1.copy_(self._jrot0 if jrot1 is None else jrot1)
             self.Je = self.joints.jacobian(pd)
-        self.contacts = self._contacts_mod.find_contacts(self.geom, pd, maxc=self.maxc, eps=self.eps)
+        self.contacts = self._contacts_mod.find_contacts(self.geom, pd, maxc=self.maxc, eps=self.eps, **self._bp)
         return self
 
     def check_capacity(self):
@@ -902,7 +910,7 @@ class ContactWorld:
         p_start = self.p
         ct.move_and_find_contacts(self.geom, p_start.detach(), v_new.detach(), self.dt, eps=self.eps, tol=self.tol,
                                   strict=self.strict, dt_floor=self.dt / 4, max_trials=self.max_trials, t=self.t, out=cb,
-                                  dt_scene=None if sub is None else sub["dt_k"])
+                                  dt_scene=None if sub is None else sub["dt_k"], **self._bp)
         # the accepted pose: the kernel's value, the gradient of p + v dt_used (a zero rotation increment carries no gradient to the geometry)
         self.v = v_new
         if js is not None:                                                 # joint.move(dt): rot1 += body1.v[0] dt (constraints.py:39-43)
@@ -939,7 +947,7 @@ class ContactWorld:
             else:
                 self.p, self._p_geom = _StateUpdate.apply(p_mid, g_mid, None, dp_s, p_corr, None, dt_used, 0.5, None)
             self._p_geom_src = self.p
-            self.contacts = ct.find_contacts(self.geom, p_corr, maxc=self.maxc, eps=self.eps)   # world.py:121
+            self.contacts = ct.find_contacts(self.geom, p_corr, maxc=self.maxc, eps=self.eps, **self._bp)   # world.py:121
             out = dict(out)
             out["post_stab"] = ps
         ret = dict(out)
@@ -1021,7 +1029,7 @@ class ContactWorld:
         self._contacts_mod.move_and_find_contacts(self.geom, self.p, self.v, self.dt, eps=self.eps, tol=self.tol,
                                                   strict=self.strict, dt_floor=self.dt / 4,
                                                   max_trials=self.max_trials, t=self.t, out=cb,
-                                                  dt_scene=sub["dt_k"] if fixed else None)
+                                                  dt_scene=sub["dt_k"] if fixed else None, **self._bp)
         self.p, cb.p_out = cb.p_out, self.p                              # accepted pose becomes the state (double buffer)
         if self.joints is not None:                                      # joint.move(dt) + the Jacobian at the new pose (world.py:91-92)
             self._Je_spare = self.joints.jacobian(self.p, v=self.v, dt_scene=cb.dt_used, out=self._Je_spare)
@@ -1036,7 +1044,7 @@ class ContactWorld:
             if self.joints is not None:                                  # the joints follow the correction move too (world.py:112-116)
                 self._Je_spare = self.joints.jacobian(self.p, v=ps["dp"], dt_scene=cb.dt_used, vscale=0.5, out=self._Je_spare)
                 self.Je, self._Je_spare = self._Je_spare, self.Je
-            self._contacts_mod.find_contacts(self.geom, self.p, maxc=self.maxc, eps=self.eps, out=cb)   # world.py:121
+            self._contacts_mod.find_contacts(self.geom, self.p, maxc=self.maxc, eps=self.eps, out=cb, **self._bp)   # world.py:121
             out["post_stab"] = ps
         ret = dict(out)
         ret["v_new"], ret["v_prev"] = self.v, out["v_new"]               # the NEW velocities; the spare buffer holds the old

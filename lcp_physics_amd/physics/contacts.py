@@ -11,6 +11,8 @@ per-scene `count`.  No CPU fallback.
 Sizes: hulls of up to 8 vertices in scenes of up to 32 bodies run on `lcp_move_find_contacts_f64` /
 `lcp_contact_frame_backward_f64` (lcp_contacts.hip); anything else, up to 64 vertices per hull (the capacity
 `verts_local.shape[2]`, 8..64), 64 bodies and 1024 hull vertices per scene, on the `_nv_` entries (lcp_contacts_wide.hip).
+`broadphase=True` (opt-in) runs the detection at all of these sizes on `lcp_move_find_contacts_bp_f64` (lcp_contacts_bp.hip): the pairs
+are culled by bounding circle and bounding box before the narrow phase, the records are the same bit for bit.
 """
 from dataclasses import dataclass
 
@@ -174,13 +176,17 @@ class ContactBuffers:
 
 
 def move_and_find_contacts(geom, p_start, v, dt, maxc=16, eps=EPSILON, tol=TOL, strict=True, dt_floor=None,
-                           max_trials=64, t=None, out=None, dt_scene=None):
+                           max_trials=64, t=None, out=None, dt_scene=None, broadphase=False, candidates=None):
     """`p <- p_start + v dt`, contacts at the new pose, dt halving while a contact penetrates by more than `tol`
     (`world.py:88-101`) for every scene.  `v=None` detects at `p_start` (the `find_contacts()` of
     `World.__init__`, `world.py:65-66`).  Returns the `ContactBuffers` (p_out = accepted pose).
     `dt_scene` [B] float64: every scene's loop starts from its own dt (`lcp_move_find_contacts_dts_f64`: the sub-steps of
     `World.step(fixed_dt=True)`, `world.py:72-80`); a scene with dt_scene <= 0 stays at `p_start` with dt_used = 0.  `dt` then only
-    sets the default `dt_floor`."""
+    sets the default `dt_floor`.
+    `broadphase=True`: the launch is `lcp_move_find_contacts_bp_f64` (lcp_contacts_bp.hip) at every size - each trial pose culls the
+    body pairs by bounding circle and bounding box (the role of the ODE space of `World.find_contacts`, `world.py:139-142`, over the
+    padded spheres of `bodies.py:_create_geom`) and only the survivors reach the narrow phase; the outputs are the same bit for bit.
+    `candidates`: an optional [B] int32 device tensor that receives the number of surviving pairs at the accepted pose."""
     lib = _lib.load()
     B, nb = geom.B, geom.nb
     _lib.require_gpu_tensor(geom.kind, "kind", torch.int32)
@@ -210,6 +216,19 @@ def move_and_find_contacts(geom, p_start, v, dt, maxc=16, eps=EPSILON, tol=TOL, 
         _lib.require_gpu_tensor(dt_scene, "dt_scene", torch.float64)
         if tuple(dt_scene.shape) != (B,):
             raise RuntimeError("dt_scene must be [B]")
+    if candidates is not None:
+        if not broadphase:
+            raise ValueError("candidates belongs to broadphase=True")
+        _lib.require_gpu_tensor(candidates, "candidates", torch.int32)
+        if tuple(candidates.shape) != (B,):
+            raise RuntimeError("candidates must be [B]")
+    if broadphase:
+        with torch.cuda.device(dev):                                        # (the real vertex total, also for a batch that is not `wide`)
+            rc = lib.lcp_move_find_contacts_bp_f64(B, nb, out.maxc, geom.nvcap, geom.verts_max(), *args, P(dt_scene), P(candidates),
+                                                   _lib.stream_ptr(dev))
+        _lib.check(rc, "lcp_move_find_contacts_bp_f64")
+        return out
+    if dt_scene is not None:
         with torch.cuda.device(dev):
             rc = lib.lcp_move_find_contacts_dts_f64(B, nb, out.maxc, geom.nvcap, 0 if not geom.wide else geom.verts_max(), *args,
                                                     P(dt_scene), _lib.stream_ptr(dev))
@@ -227,9 +246,11 @@ def move_and_find_contacts(geom, p_start, v, dt, maxc=16, eps=EPSILON, tol=TOL, 
     return out
 
 
-def find_contacts(geom, p, maxc=16, eps=EPSILON, out=None):
-    """`World.find_contacts` (`world.py:139-142`) for every scene at pose `p` [B,nb,3] (float64)."""
-    return move_and_find_contacts(geom, p, None, 0.0, maxc=maxc, eps=eps, out=out, max_trials=1)
+def find_contacts(geom, p, maxc=16, eps=EPSILON, out=None, broadphase=False, candidates=None):
+    """`World.find_contacts` (`world.py:139-142`) for every scene at pose `p` [B,nb,3] (float64); `broadphase`, `candidates`: see
+    `move_and_find_contacts`."""
+    return move_and_find_contacts(geom, p, None, 0.0, maxc=maxc, eps=eps, out=out, max_trials=1, broadphase=broadphase,
+                                  candidates=candidates)
 
 
 def contact_frame_backward(geom, p, cb, g_n, g_p1, g_p2, eps=EPSILON):
