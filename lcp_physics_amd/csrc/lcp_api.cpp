@@ -184,6 +184,23 @@ inline Route route_dense(int nz, int m, int e, const Word& w) {
   return r;
 }
 
+// lcp_move_find_contacts_*: which kernels serve a detection call of these sizes.  The limits themselves are the two predicates'
+// (lcp_contacts.hip: <= 32 bodies, capacity 8; lcp_contacts_wide.hip: <= 64 bodies, capacity 8..64, <= 1024 vertices per scene).
+enum DetectEntry { DETECT_F64, DETECT_NV, DETECT_DTS, DETECT_BP };      // lcp_move_find_contacts_f64, _nv_f64, _dts_f64, _bp_f64
+enum DetectKernels { DETECT_NONE, DETECT_SMALL, DETECT_WIDE, DETECT_BROADPHASE };   // lcp_contacts.hip, lcp_contacts_wide.hip, lcp_contacts_bp.hip
+inline DetectKernels route_contacts(DetectEntry entry, int nb, int nvcap, int scene_verts_max) {
+  const bool small = lcp::contacts_small_supported(nb, nvcap);
+  const bool wide = lcp::contacts_wide_supported(nb, nvcap, scene_verts_max);
+  switch (entry) {
+    case DETECT_F64: return small ? DETECT_SMALL : DETECT_NONE;
+    // the wide kernel at every size it accepts, the sizes of the small kernels included (callers compare the two there)
+    case DETECT_NV: return wide ? DETECT_WIDE : DETECT_NONE;
+    // the limits of lcp_move_find_contacts_nv_f64, whichever kernel serves the call
+    case DETECT_DTS: return !wide ? DETECT_NONE : small ? DETECT_SMALL : DETECT_WIDE;
+    default: return wide ? DETECT_BROADPHASE : DETECT_NONE;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -527,24 +544,48 @@ int lcp_post_stabilization_backward_f32(int B, int nb, int maxc, int e, const fl
   }
 }
 
-
-int lcp_move_find_contacts_f64(int B, int nb, int maxc, const int32_t* kind, const double* radius,
-                               const double* verts_local, const int32_t* nverts, const uint8_t* no_contact,
-                               const double* p_start, const float* v, double dt, double dt_floor, int strict,
-                               int max_trials, double eps, double tol, double* p_out, float* c_n, float* c_p1,
-                               float* c_p2, double* c_pen, int32_t* c_i1, int32_t* c_i2, int32_t* count,
-                               double* max_pen, double* dt_used, double* t, int32_t* trials, void* stream) {
+// What the four detection entries share: the checks of their common arguments and the one fill of the kernel argument.
+// `dt_scene`: the dt each scene's loop starts from, or NULL = `dt` everywhere.
+static int fill_contacts(lcp::ContactArgs& P, int B, int nb, int maxc, const int32_t* kind, const double* radius,
+                         const double* verts_local, const int32_t* nverts, const uint8_t* no_contact, const double* p_start,
+                         const float* v, double dt, double dt_floor, int strict, int max_trials, double eps, double tol,
+                         double* p_out, float* c_n, float* c_p1, float* c_p2, double* c_pen, int32_t* c_i1, int32_t* c_i2,
+                         int32_t* count, double* max_pen, double* dt_used, double* t, int32_t* trials, const double* dt_scene) {
   if (B <= 0 || nb <= 0 || maxc <= 0 || max_trials <= 0) return LCP_E_BADARG;
   if (!kind || !radius || !verts_local || !nverts || !p_start) return LCP_E_BADARG;
   if (!c_n || !c_p1 || !c_p2 || !c_i1 || !c_i2 || !count) return LCP_E_BADARG;
-  lcp::ContactArgs P;
   memset(&P, 0, sizeof(P));
   P.B = B; P.nb = nb; P.maxc = maxc; P.kind = kind; P.nverts = nverts; P.radius = radius;
   P.verts_local = verts_local; P.no_contact = no_contact; P.p_start = p_start; P.v = v;
   P.dt = dt; P.dt_floor = dt_floor; P.eps = eps; P.tol = tol; P.strict = strict; P.max_trials = max_trials;
   P.p_out = p_out; P.c_n = c_n; P.c_p1 = c_p1; P.c_p2 = c_p2; P.c_pen = c_pen; P.c_i1 = c_i1; P.c_i2 = c_i2;
   P.count = count; P.max_pen = max_pen; P.dt_used = dt_used; P.t = t; P.trials = trials;
-  return lcp::contacts_launch(P, stream);
+  P.dt_in = dt_scene;
+  return 0;
+}
+
+// a detection call on the kernels route_contacts gives it (after every LCP_E_BADARG check of the entry)
+static int launch_contacts(DetectEntry entry, const lcp::ContactArgs& P, int nvcap, int scene_verts_max, int32_t* candidates,
+                           void* stream) {
+  switch (route_contacts(entry, P.nb, nvcap, scene_verts_max)) {
+    case DETECT_SMALL: return lcp::contacts_launch(P, stream);
+    case DETECT_WIDE: return lcp::contacts_wide_launch(P, nvcap, scene_verts_max, stream);
+    case DETECT_BROADPHASE: return lcp::contacts_bp_launch(P, nvcap, scene_verts_max, candidates, stream);
+    default: return LCP_E_TOOLARGE;
+  }
+}
+
+// (verts_local [B, nb, 8, 2]: this entry has no capacity argument)
+int lcp_move_find_contacts_f64(int B, int nb, int maxc, const int32_t* kind, const double* radius,
+                               const double* verts_local, const int32_t* nverts, const uint8_t* no_contact,
+                               const double* p_start, const float* v, double dt, double dt_floor, int strict,
+                               int max_trials, double eps, double tol, double* p_out, float* c_n, float* c_p1,
+                               float* c_p2, double* c_pen, int32_t* c_i1, int32_t* c_i2, int32_t* count,
+                               double* max_pen, double* dt_used, double* t, int32_t* trials, void* stream) {
+  lcp::ContactArgs P;
+  const int rc = fill_contacts(P, B, nb, maxc, kind, radius, verts_local, nverts, no_contact, p_start, v, dt, dt_floor, strict, max_trials, eps, tol,
+                               p_out, c_n, c_p1, c_p2, c_pen, c_i1, c_i2, count, max_pen, dt_used, t, trials, nullptr);
+  return rc ? rc : launch_contacts(DETECT_F64, P, /*nvcap*/ 8, 0, nullptr, stream);
 }
 
 int lcp_joint_jacobian_f64(int B, int nb, int nj, int e, const int32_t* jtype, const int32_t* jb1, const int32_t* jb2,
@@ -570,12 +611,18 @@ int lcp_state_update_backward_f64(int B, int nb, int nj, const double* g_p, cons
   return lcp::state_update_backward_launch(B, nb, nj, g_p, g_g, g_rot, v, dt_scene, scale, jtype, jb1, g_v, stream);
 }
 
+// what the three contact-frame backward entries share: sizes, geometry, pose, and the records' counts and cotangents
+static bool frame_args_ok(int B, int nb, int maxc, const int32_t* kind, const double* radius, const double* verts_local,
+                          const int32_t* nverts, const double* p, const int32_t* count, const float* g_n, const float* g_p1,
+                          const float* g_p2) {
+  return B > 0 && nb > 0 && maxc > 0 && kind && radius && verts_local && nverts && p && count && g_n && g_p1 && g_p2;
+}
+
 int lcp_contact_frame_backward_f64(int B, int nb, int maxc, const int32_t* kind, const double* radius, const double* verts_local,
                                    const int32_t* nverts, const uint8_t* no_contact, const double* p, double eps,
                                    const int32_t* count, const float* g_n, const float* g_p1, const float* g_p2, double* dp,
                                    void* stream) {
-  if (B <= 0 || nb <= 0 || maxc <= 0) return LCP_E_BADARG;
-  if (!kind || !radius || !verts_local || !nverts || !p || !count || !g_n || !g_p1 || !g_p2 || !dp) return LCP_E_BADARG;
+  if (!frame_args_ok(B, nb, maxc, kind, radius, verts_local, nverts, p, count, g_n, g_p1, g_p2) || !dp) return LCP_E_BADARG;
   return lcp::contact_frame_backward_launch(B, nb, maxc, kind, radius, verts_local, nverts, no_contact, p, eps, count, g_n, g_p1, g_p2,
                                             dp, stream);
 }
@@ -586,17 +633,11 @@ int lcp_move_find_contacts_nv_f64(int B, int nb, int maxc, int nvcap, int scene_
                                   int max_trials, double eps, double tol, double* p_out, float* c_n, float* c_p1,
                                   float* c_p2, double* c_pen, int32_t* c_i1, int32_t* c_i2, int32_t* count,
                                   double* max_pen, double* dt_used, double* t, int32_t* trials, void* stream) {
-  if (B <= 0 || nb <= 0 || maxc <= 0 || max_trials <= 0 || scene_verts_max < 0) return LCP_E_BADARG;
-  if (!kind || !radius || !verts_local || !nverts || !p_start) return LCP_E_BADARG;
-  if (!c_n || !c_p1 || !c_p2 || !c_i1 || !c_i2 || !count) return LCP_E_BADARG;
+  if (scene_verts_max < 0) return LCP_E_BADARG;
   lcp::ContactArgs P;
-  memset(&P, 0, sizeof(P));
-  P.B = B; P.nb = nb; P.maxc = maxc; P.kind = kind; P.nverts = nverts; P.radius = radius;
-  P.verts_local = verts_local; P.no_contact = no_contact; P.p_start = p_start; P.v = v;
-  P.dt = dt; P.dt_floor = dt_floor; P.eps = eps; P.tol = tol; P.strict = strict; P.max_trials = max_trials;
-  P.p_out = p_out; P.c_n = c_n; P.c_p1 = c_p1; P.c_p2 = c_p2; P.c_pen = c_pen; P.c_i1 = c_i1; P.c_i2 = c_i2;
-  P.count = count; P.max_pen = max_pen; P.dt_used = dt_used; P.t = t; P.trials = trials;
-  return lcp::contacts_wide_launch(P, nvcap, scene_verts_max, stream);
+  const int rc = fill_contacts(P, B, nb, maxc, kind, radius, verts_local, nverts, no_contact, p_start, v, dt, dt_floor, strict, max_trials, eps, tol,
+                               p_out, c_n, c_p1, c_p2, c_pen, c_i1, c_i2, count, max_pen, dt_used, t, trials, nullptr);
+  return rc ? rc : launch_contacts(DETECT_NV, P, nvcap, scene_verts_max, nullptr, stream);
 }
 
 // World.step(fixed_dt=True) (world.py:72-80): step_dt(end_t - t) with a dt of its own per scene
@@ -606,21 +647,11 @@ int lcp_move_find_contacts_dts_f64(int B, int nb, int maxc, int nvcap, int scene
                                    int max_trials, double eps, double tol, double* p_out, float* c_n, float* c_p1,
                                    float* c_p2, double* c_pen, int32_t* c_i1, int32_t* c_i2, int32_t* count,
                                    double* max_pen, double* dt_used, double* t, int32_t* trials, const double* dt_scene, void* stream) {
-  if (B <= 0 || nb <= 0 || maxc <= 0 || max_trials <= 0 || scene_verts_max < 0) return LCP_E_BADARG;
-  if (!kind || !radius || !verts_local || !nverts || !p_start || !dt_scene) return LCP_E_BADARG;
-  if (!c_n || !c_p1 || !c_p2 || !c_i1 || !c_i2 || !count) return LCP_E_BADARG;
+  if (scene_verts_max < 0 || !dt_scene) return LCP_E_BADARG;
   lcp::ContactArgs P;
-  memset(&P, 0, sizeof(P));
-  P.B = B; P.nb = nb; P.maxc = maxc; P.kind = kind; P.nverts = nverts; P.radius = radius;
-  P.verts_local = verts_local; P.no_contact = no_contact; P.p_start = p_start; P.v = v;
-  P.dt = dt; P.dt_floor = dt_floor; P.eps = eps; P.tol = tol; P.strict = strict; P.max_trials = max_trials;
-  P.p_out = p_out; P.c_n = c_n; P.c_p1 = c_p1; P.c_p2 = c_p2; P.c_pen = c_pen; P.c_i1 = c_i1; P.c_i2 = c_i2;
-  P.count = count; P.max_pen = max_pen; P.dt_used = dt_used; P.t = t; P.trials = trials;
-  P.dt_in = dt_scene;
-  // (the limits of lcp_move_find_contacts_nv_f64, whichever kernel serves the call)
-  if (nb > 64 || nvcap < 8 || nvcap > 64 || scene_verts_max > lcp::CONTACTS_WIDE_MAX_SCENE_VERTS) return LCP_E_TOOLARGE;
-  if (nb <= 32 && nvcap == 8) return lcp::contacts_launch(P, stream);
-  return lcp::contacts_wide_launch(P, nvcap, scene_verts_max, stream);
+  const int rc = fill_contacts(P, B, nb, maxc, kind, radius, verts_local, nverts, no_contact, p_start, v, dt, dt_floor, strict, max_trials, eps, tol,
+                               p_out, c_n, c_p1, c_p2, c_pen, c_i1, c_i2, count, max_pen, dt_used, t, trials, dt_scene);
+  return rc ? rc : launch_contacts(DETECT_DTS, P, nvcap, scene_verts_max, nullptr, stream);
 }
 
 // the same loop with a broadphase in front of the narrow phase (lcp_contacts_bp.hip); dt_scene NULL: the scalar dt
@@ -631,18 +662,11 @@ int lcp_move_find_contacts_bp_f64(int B, int nb, int maxc, int nvcap, int scene_
                                   float* c_p2, double* c_pen, int32_t* c_i1, int32_t* c_i2, int32_t* count,
                                   double* max_pen, double* dt_used, double* t, int32_t* trials, const double* dt_scene,
                                   int32_t* candidates, void* stream) {
-  if (B <= 0 || nb <= 0 || maxc <= 0 || max_trials <= 0 || scene_verts_max < 0) return LCP_E_BADARG;
-  if (!kind || !radius || !verts_local || !nverts || !p_start) return LCP_E_BADARG;
-  if (!c_n || !c_p1 || !c_p2 || !c_i1 || !c_i2 || !count) return LCP_E_BADARG;
+  if (scene_verts_max < 0) return LCP_E_BADARG;
   lcp::ContactArgs P;
-  memset(&P, 0, sizeof(P));
-  P.B = B; P.nb = nb; P.maxc = maxc; P.kind = kind; P.nverts = nverts; P.radius = radius;
-  P.verts_local = verts_local; P.no_contact = no_contact; P.p_start = p_start; P.v = v;
-  P.dt = dt; P.dt_floor = dt_floor; P.eps = eps; P.tol = tol; P.strict = strict; P.max_trials = max_trials;
-  P.p_out = p_out; P.c_n = c_n; P.c_p1 = c_p1; P.c_p2 = c_p2; P.c_pen = c_pen; P.c_i1 = c_i1; P.c_i2 = c_i2;
-  P.count = count; P.max_pen = max_pen; P.dt_used = dt_used; P.t = t; P.trials = trials;
-  P.dt_in = dt_scene;
-  return lcp::contacts_bp_launch(P, nvcap, scene_verts_max, candidates, stream);     // (checks the sizes before it launches)
+  const int rc = fill_contacts(P, B, nb, maxc, kind, radius, verts_local, nverts, no_contact, p_start, v, dt, dt_floor, strict, max_trials, eps, tol,
+                               p_out, c_n, c_p1, c_p2, c_pen, c_i1, c_i2, count, max_pen, dt_used, t, trials, dt_scene);
+  return rc ? rc : launch_contacts(DETECT_BP, P, nvcap, scene_verts_max, candidates, stream);
 }
 
 // the bookkeeping of world.py:72-80 around one sub-step (lcp_substep.hip)
@@ -664,8 +688,8 @@ int lcp_contact_frame_backward_nv_f64(int B, int nb, int maxc, int nvcap, int sc
                                       double eps, const int32_t* count, const int32_t* c_i1, const int32_t* c_i2, const float* g_n,
                                       const float* g_p1, const float* g_p2, double* dp, void* stream) {
   (void)no_contact;                                            // (the records name the pairs; a masked pair has none)
-  if (B <= 0 || nb <= 0 || maxc <= 0 || scene_verts_max < 0) return LCP_E_BADARG;
-  if (!kind || !radius || !verts_local || !nverts || !p || !count || !c_i1 || !c_i2 || !g_n || !g_p1 || !g_p2 || !dp) return LCP_E_BADARG;
+  if (!frame_args_ok(B, nb, maxc, kind, radius, verts_local, nverts, p, count, g_n, g_p1, g_p2)) return LCP_E_BADARG;
+  if (scene_verts_max < 0 || !c_i1 || !c_i2 || !dp) return LCP_E_BADARG;
   return lcp::contact_frame_backward_wide_launch(B, nb, maxc, nvcap, scene_verts_max, kind, radius, verts_local, nverts, p, eps, count,
                                                  c_i1, c_i2, g_n, g_p1, g_p2, dp, stream);
 }
@@ -674,8 +698,8 @@ int lcp_contact_frame_backward_shape_f64(int B, int nb, int maxc, int nvcap, int
                                          const double* verts_local, const int32_t* nverts, const double* p, double eps,
                                          const int32_t* count, const int32_t* c_i1, const int32_t* c_i2, const float* g_n,
                                          const float* g_p1, const float* g_p2, double* d_radius, double* d_verts_local, void* stream) {
-  if (B <= 0 || nb <= 0 || maxc <= 0 || scene_verts_max < 0) return LCP_E_BADARG;
-  if (!kind || !radius || !verts_local || !nverts || !p || !count || !c_i1 || !c_i2 || !g_n || !g_p1 || !g_p2) return LCP_E_BADARG;
+  if (!frame_args_ok(B, nb, maxc, kind, radius, verts_local, nverts, p, count, g_n, g_p1, g_p2)) return LCP_E_BADARG;
+  if (scene_verts_max < 0 || !c_i1 || !c_i2) return LCP_E_BADARG;
   if (!d_radius && !d_verts_local) return LCP_E_BADARG;         // (nothing asked for)
   return lcp::contact_frame_backward_shape_launch(B, nb, maxc, nvcap, scene_verts_max, kind, radius, verts_local, nverts, p, eps, count,
                                                   c_i1, c_i2, g_n, g_p1, g_p2, d_radius, d_verts_local, stream);

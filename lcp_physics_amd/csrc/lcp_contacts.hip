@@ -409,7 +409,17 @@ __global__ void __launch_bounds__(64) lcp_state_update_backward_kernel(int B, in
   }
 }
 
+// the instantiation of the detection kernel for P.nb bodies: four scenes per wave up to 6 bodies, one scene per wave beyond
+template <bool DTS>
+static void launch_detection(const ContactArgs& P, hipStream_t stream) {
+  if (P.nb <= 6) hipLaunchKernelGGL((lcp_move_find_contacts_kernel<16, 6, DTS>), dim3((P.B + 3) / 4), dim3(64), 0, stream, P);
+  else if (P.nb <= 16) hipLaunchKernelGGL((lcp_move_find_contacts_kernel<64, 16, DTS>), dim3(P.B), dim3(64), 0, stream, P);
+  else hipLaunchKernelGGL((lcp_move_find_contacts_kernel<64, MAXB, DTS>), dim3(P.B), dim3(64), 0, stream, P);   // (15 KB of LDS per scene)
+}
+
 }  // namespace ct
+
+bool contacts_small_supported(int nb, int nvcap) { return nb >= 1 && nb <= ct::MAXB && nvcap == ct::NV; }
 
 int joint_jacobian_backward_launch(int B, int nb, int nj, int e, const int32_t* jtype, const int32_t* jb1, const int32_t* jb2,
                                    const double* jr1, const double* jrot1, const float* gJe, double* g_p, double* g_rot, void* stream) {
@@ -437,22 +447,16 @@ int contact_frame_backward_launch(int B, int nb, int maxc, const int32_t* kind, 
                                   const int32_t* nverts, const uint8_t* no_contact, const double* p, double eps,
                                   const int32_t* count, const float* g_n, const float* g_p1, const float* g_p2, double* dp,
                                   void* stream) {
-  if (nb > ct::MAXB) return LCP_E_TOOLARGE;
+  if (!contacts_small_supported(nb, ct::NV)) return LCP_E_TOOLARGE;
   hipLaunchKernelGGL(ct::lcp_contact_frame_backward_kernel, dim3((B + ct::FB_T - 1) / ct::FB_T), dim3(ct::FB_T), 0, (hipStream_t)stream, B, nb, maxc, kind,
                      radius, verts_local, nverts, no_contact, p, eps, count, g_n, g_p1, g_p2, dp);
   return hipGetLastError() == hipSuccess ? 0 : LCP_E_LAUNCH;
 }
 
 int contacts_launch(const ContactArgs& P, void* stream) {
-  if (P.nb > ct::MAXB) return LCP_E_TOOLARGE;
-  if (P.dt_in) {
-    if (P.nb <= 6) hipLaunchKernelGGL((ct::lcp_move_find_contacts_kernel<16, 6, true>), dim3((P.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, P);
-    else if (P.nb <= 16) hipLaunchKernelGGL((ct::lcp_move_find_contacts_kernel<64, 16, true>), dim3(P.B), dim3(64), 0, (hipStream_t)stream, P);
-    else hipLaunchKernelGGL((ct::lcp_move_find_contacts_kernel<64, ct::MAXB, true>), dim3(P.B), dim3(64), 0, (hipStream_t)stream, P);
-  }
-  else if (P.nb <= 6) hipLaunchKernelGGL((ct::lcp_move_find_contacts_kernel<16, 6, false>), dim3((P.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, P);
-  else if (P.nb <= 16) hipLaunchKernelGGL((ct::lcp_move_find_contacts_kernel<64, 16, false>), dim3(P.B), dim3(64), 0, (hipStream_t)stream, P);
-  else hipLaunchKernelGGL((ct::lcp_move_find_contacts_kernel<64, ct::MAXB, false>), dim3(P.B), dim3(64), 0, (hipStream_t)stream, P);   // (15 KB of LDS per scene)
+  if (!contacts_small_supported(P.nb, ct::NV)) return LCP_E_TOOLARGE;
+  if (P.dt_in) ct::launch_detection<true>(P, (hipStream_t)stream);
+  else ct::launch_detection<false>(P, (hipStream_t)stream);
   return hipGetLastError() == hipSuccess ? 0 : LCP_E_LAUNCH;
 }
 

@@ -257,23 +257,14 @@ __global__ void __launch_bounds__(64) lcp_move_find_contacts_bp_kernel(ContactAr
   }
 }
 
-static size_t detect_lds(int vmax) { return (size_t)vmax * (3 * sizeof(V2) + sizeof(double) + sizeof(int)); }
-
 }  // namespace bp
 }  // namespace ctw
 
 int contacts_bp_launch(const ContactArgs& P, int nvcap, int scene_verts_max, int32_t* candidates, void* stream) {
-  if (!ctw::wide_sizes_ok(P.nb, nvcap, scene_verts_max)) return LCP_E_TOOLARGE;
-  const int vmax = scene_verts_max < 1 ? 1 : scene_verts_max;
-  const size_t lds = ctw::bp::detect_lds(vmax);
-  if (P.dt_in) {
-    if (ctw::set_lds(ctw::bp::lcp_move_find_contacts_bp_kernel<true>, lds)) return LCP_E_LAUNCH;
-    hipLaunchKernelGGL(ctw::bp::lcp_move_find_contacts_bp_kernel<true>, dim3(P.B), dim3(64), lds, (hipStream_t)stream, P, nvcap, vmax, candidates);
-  } else {
-    if (ctw::set_lds(ctw::bp::lcp_move_find_contacts_bp_kernel<false>, lds)) return LCP_E_LAUNCH;
-    hipLaunchKernelGGL(ctw::bp::lcp_move_find_contacts_bp_kernel<false>, dim3(P.B), dim3(64), lds, (hipStream_t)stream, P, nvcap, vmax, candidates);
-  }
-  return hipGetLastError() == hipSuccess ? 0 : LCP_E_LAUNCH;
+  if (!contacts_wide_supported(P.nb, nvcap, scene_verts_max)) return LCP_E_TOOLARGE;
+  const int vmax = ctw::vmax_of(scene_verts_max);
+  const auto kernel = P.dt_in ? ctw::bp::lcp_move_find_contacts_bp_kernel<true> : ctw::bp::lcp_move_find_contacts_bp_kernel<false>;
+  return ctw::launch_per_scene(kernel, P.B, 64, ctw::detect_lds(vmax), stream, P, nvcap, vmax, candidates);
 }
 
 }  // namespace lcp

@@ -284,14 +284,12 @@ int contact_frame_backward_shape_launch(int B, int nb, int maxc, int nvcap, int 
                                         double eps, const int32_t* count, const int32_t* c_i1, const int32_t* c_i2,
                                         const float* g_n, const float* g_p1, const float* g_p2, double* d_radius,
                                         double* d_verts_local, void* stream) {
-  if (!ctw::wide_sizes_ok(nb, nvcap, scene_verts_max)) return LCP_E_TOOLARGE;
-  const int vmax = scene_verts_max < 1 ? 1 : scene_verts_max;
+  if (!contacts_wide_supported(nb, nvcap, scene_verts_max)) return LCP_E_TOOLARGE;
+  const int vmax = ctw::vmax_of(scene_verts_max);
   const size_t lds = ctw::shp::shape_bwd_lds(vmax, maxc);
   if (lds > ctw::LDS_LIMIT) return LCP_E_TOOLARGE;
-  if (ctw::set_lds(ctw::shp::lcp_contact_frame_backward_shape_kernel, lds)) return LCP_E_LAUNCH;
-  hipLaunchKernelGGL(ctw::shp::lcp_contact_frame_backward_shape_kernel, dim3(B), dim3(ctw::shp::SB_T), lds, (hipStream_t)stream, nb, maxc,
-                     nvcap, vmax, kind, radius, verts_local, nverts, p, eps, count, c_i1, c_i2, g_n, g_p1, g_p2, d_radius, d_verts_local);
-  return hipGetLastError() == hipSuccess ? 0 : LCP_E_LAUNCH;
+  return ctw::launch_per_scene(ctw::shp::lcp_contact_frame_backward_shape_kernel, B, ctw::shp::SB_T, lds, stream, nb, maxc, nvcap, vmax, kind,
+                               radius, verts_local, nverts, p, eps, count, c_i1, c_i2, g_n, g_p1, g_p2, d_radius, d_verts_local);
 }
 
 }  // namespace lcp

@@ -55,18 +55,24 @@ __device__ __forceinline__ int stage_bodies(int scene, int nb, int nvcap, const 
   return __shfl(incl, 63, 64);
 }
 
+// ---- host side: what the launchers of these kernels share (the size limits themselves: contacts_wide_supported) -----------
 constexpr size_t LDS_LIMIT = 160 * 1024 - 8 * 1024;    // (the static tables of the kernels take less than 8 KB)
 
-template <typename K>
-static int set_lds(K kernel, size_t bytes) {
-  if (bytes > 64 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
-    return LCP_E_LAUNCH;
-  return 0;
-}
+// the `vmax` the kernels carve their dynamic arrays by: the caller's scene_verts_max, at least one slot
+static int vmax_of(int scene_verts_max) { return scene_verts_max < 1 ? 1 : scene_verts_max; }
 
-static bool wide_sizes_ok(int nb, int nvcap, int vmax) {
-  return nb >= 1 && nb <= MAXB && nvcap >= 8 && nvcap <= NV && vmax >= 0 && vmax <= CONTACTS_WIDE_MAX_SCENE_VERTS;
+// dynamic LDS of the detection kernels (lcp_contacts_wide.hip, lcp_contacts_bp.hip): local and rotated vertices and edge normals
+// (V2 = two doubles), edge lengths, owning bodies
+static size_t detect_lds(int vmax) { return (size_t)vmax * (3 * sizeof(double2) + sizeof(double) + sizeof(int)); }
+
+// One workgroup of `threads` per scene with `lds` bytes of dynamic LDS (opted in to beyond the 64 KB every kernel may have)
+template <typename K, typename... A>
+static int launch_per_scene(K kernel, int B, int threads, size_t lds, void* stream, A... args) {
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return LCP_E_LAUNCH;
+  hipLaunchKernelGGL(kernel, dim3(B), dim3(threads), lds, (hipStream_t)stream, args...);
+  return hipGetLastError() == hipSuccess ? 0 : LCP_E_LAUNCH;
 }
 
 }  // namespace ctw

@@ -329,39 +329,34 @@ __global__ void __launch_bounds__(FB_T) lcp_contact_frame_backward_wide_kernel(i
   }
 }
 
-static size_t detect_lds(int vmax) { return (size_t)vmax * (3 * sizeof(V2) + sizeof(double) + sizeof(int)); }
 static size_t frame_bwd_lds(int vmax, int maxc) {
   return (size_t)vmax * (2 * sizeof(double2) + sizeof(double)) + (size_t)maxc * 6 * sizeof(double) + (size_t)(3 * maxc + 1) * sizeof(int);
 }
 
 }  // namespace ctw
 
+bool contacts_wide_supported(int nb, int nvcap, int scene_verts_max) {
+  return nb >= 1 && nb <= ctw::MAXB && nvcap >= 8 && nvcap <= ctw::NV && scene_verts_max >= 0 &&
+         scene_verts_max <= CONTACTS_WIDE_MAX_SCENE_VERTS;
+}
+
 int contacts_wide_launch(const ContactArgs& P, int nvcap, int scene_verts_max, void* stream) {
-  if (!ctw::wide_sizes_ok(P.nb, nvcap, scene_verts_max)) return LCP_E_TOOLARGE;
-  const int vmax = scene_verts_max < 1 ? 1 : scene_verts_max;
-  const size_t lds = ctw::detect_lds(vmax);
-  if (P.dt_in) {
-    if (ctw::set_lds(ctw::lcp_move_find_contacts_wide_kernel<true>, lds)) return LCP_E_LAUNCH;
-    hipLaunchKernelGGL(ctw::lcp_move_find_contacts_wide_kernel<true>, dim3(P.B), dim3(64), lds, (hipStream_t)stream, P, nvcap, vmax);
-  } else {
-    if (ctw::set_lds(ctw::lcp_move_find_contacts_wide_kernel<false>, lds)) return LCP_E_LAUNCH;
-    hipLaunchKernelGGL(ctw::lcp_move_find_contacts_wide_kernel<false>, dim3(P.B), dim3(64), lds, (hipStream_t)stream, P, nvcap, vmax);
-  }
-  return hipGetLastError() == hipSuccess ? 0 : LCP_E_LAUNCH;
+  if (!contacts_wide_supported(P.nb, nvcap, scene_verts_max)) return LCP_E_TOOLARGE;
+  const int vmax = ctw::vmax_of(scene_verts_max);
+  const auto kernel = P.dt_in ? ctw::lcp_move_find_contacts_wide_kernel<true> : ctw::lcp_move_find_contacts_wide_kernel<false>;
+  return ctw::launch_per_scene(kernel, P.B, 64, ctw::detect_lds(vmax), stream, P, nvcap, vmax);
 }
 
 int contact_frame_backward_wide_launch(int B, int nb, int maxc, int nvcap, int scene_verts_max, const int32_t* kind,
                                        const double* radius, const double* verts_local, const int32_t* nverts, const double* p,
                                        double eps, const int32_t* count, const int32_t* c_i1, const int32_t* c_i2,
                                        const float* g_n, const float* g_p1, const float* g_p2, double* dp, void* stream) {
-  if (!ctw::wide_sizes_ok(nb, nvcap, scene_verts_max)) return LCP_E_TOOLARGE;
-  const int vmax = scene_verts_max < 1 ? 1 : scene_verts_max;
+  if (!contacts_wide_supported(nb, nvcap, scene_verts_max)) return LCP_E_TOOLARGE;
+  const int vmax = ctw::vmax_of(scene_verts_max);
   const size_t lds = ctw::frame_bwd_lds(vmax, maxc);
   if (lds > ctw::LDS_LIMIT) return LCP_E_TOOLARGE;
-  if (ctw::set_lds(ctw::lcp_contact_frame_backward_wide_kernel, lds)) return LCP_E_LAUNCH;
-  hipLaunchKernelGGL(ctw::lcp_contact_frame_backward_wide_kernel, dim3(B), dim3(ctw::FB_T), lds, (hipStream_t)stream, nb, maxc, nvcap, vmax,
-                     kind, radius, verts_local, nverts, p, eps, count, c_i1, c_i2, g_n, g_p1, g_p2, dp);
-  return hipGetLastError() == hipSuccess ? 0 : LCP_E_LAUNCH;
+  return ctw::launch_per_scene(ctw::lcp_contact_frame_backward_wide_kernel, B, ctw::FB_T, lds, stream, nb, maxc, nvcap, vmax, kind, radius,
+                               verts_local, nverts, p, eps, count, c_i1, c_i2, g_n, g_p1, g_p2, dp);
 }
 
 }  // namespace lcp

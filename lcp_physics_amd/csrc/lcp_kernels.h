@@ -130,7 +130,7 @@ struct StepBwdArgs {
 struct ContactArgs {
   int B, nb, maxc;
   const int32_t *kind, *nverts;         // [B, nb]  0 = circle, 1 = hull ; vertex count of a hull
-  const double *radius, *verts_local;   // [B, nb], [B, nb, 8, 2] (body frame)
+  const double *radius, *verts_local;   // [B, nb], [B, nb, nvcap, 2] (body frame; nvcap = 8 on the kernels of lcp_contacts.hip)
   const uint8_t* no_contact;            // [B, nb, nb] pairs to skip, or NULL
   const double* p_start;                // [B, nb, 3] (rot, x, y)
   const float* v;                       // [B, nb, 3] or NULL (detect at p_start)
@@ -218,6 +218,7 @@ int big_dense_forward(const FwdArgs& P, int32_t* cls, size_t ws_scene, int prima
 int big_dense_backward(const BwdArgs& P, int32_t* cls, size_t ws_scene, void* stream);
 
 // narrow-phase contact generation + position update - lcp_contacts.hip
+bool contacts_small_supported(int nb, int nvcap);     // <= 32 bodies, hulls of capacity 8 (detection and the frame backward)
 int contacts_launch(const ContactArgs& P, void* stream);
 int joint_jacobian_launch(int B, int nb, int nj, int e, const int32_t* jtype, const int32_t* jb1, const int32_t* jb2, const double* jr1,
                           double* jrot1, const double* p, const float* v, const double* dt_scene, double dt, double vscale, float* Je,
@@ -237,6 +238,7 @@ int substep_commit_launch(int B, int nb, const int32_t* active, const float* v_o
 // the same for hulls of up to 64 vertices (verts_local[B,nb,nvcap,2], 8 <= nvcap <= 64), up to 64 bodies and
 // CONTACTS_WIDE_MAX_SCENE_VERTS vertices per scene (packed per-scene vertex lists in LDS) - lcp_contacts_wide.hip
 constexpr int CONTACTS_WIDE_MAX_SCENE_VERTS = 1024;
+bool contacts_wide_supported(int nb, int nvcap, int scene_verts_max);   // the sizes of every kernel over the packed vertex list
 int contacts_wide_launch(const ContactArgs& P, int nvcap, int scene_verts_max, void* stream);
 int contact_frame_backward_wide_launch(int B, int nb, int maxc, int nvcap, int scene_verts_max, const int32_t* kind,
                                        const double* radius, const double* verts_local, const int32_t* nverts, const double* p,

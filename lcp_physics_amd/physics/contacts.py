@@ -175,6 +175,36 @@ class ContactBuffers:
         return new
 
 
+def _check_geometry(geom, p, name):
+    """The geometry tensors every entry reads and the pose they are evaluated at (`name`, [B,nb,3] float64).  Returns B, nb."""
+    B, nb, cap = geom.B, geom.nb, geom.nvcap
+    _lib.require_gpu_tensor(geom.kind, "kind", torch.int32)
+    _lib.require_gpu_tensor(geom.nverts, "nverts", torch.int32)
+    _lib.require_gpu_tensor(geom.radius, "radius", torch.float64)
+    _lib.require_gpu_tensor(geom.verts_local, "verts_local", torch.float64)
+    _lib.require_gpu_tensor(p, name, torch.float64)
+    if tuple(p.shape) != (B, nb, 3) or tuple(geom.verts_local.shape) != (B, nb, cap, 2) or not NV <= cap <= NV_MAX:
+        raise RuntimeError("%s must be [B,nb,3] and verts_local [B,nb,cap,2] with %d <= cap <= %d" % (name, NV, NV_MAX))
+    if geom.no_contact is not None:
+        _lib.require_gpu_tensor(geom.no_contact, "no_contact", torch.uint8)
+    return B, nb
+
+
+def _entry(geom, stem, sizes, dt_scene=None, broadphase=False, candidates=None):
+    """Which C entry serves a call: its symbol, its leading size arguments (`sizes` = B, nb, maxc, then the vertex capacity and the
+    scene's vertex total where the entry takes them) and what follows the common arguments, the stream apart.  `stem`:
+    "lcp_move_find_contacts" or "lcp_contact_frame_backward" (which has neither a per-scene dt nor a broadphase).  The kernels behind
+    each symbol: `route_contacts` in lcp_api.cpp.  `geom.verts_max()` may synchronise once, so only the routes whose kernels need the
+    vertex total evaluate it (`ContactWorld` captures its steps into HIP graphs)."""
+    if broadphase:                                      # (the real vertex total, also for a batch that is not `wide`)
+        return stem + "_bp_f64", sizes + (geom.nvcap, geom.verts_max()), (_lib.ptr(dt_scene), _lib.ptr(candidates))
+    if dt_scene is not None:
+        return stem + "_dts_f64", sizes + (geom.nvcap, geom.verts_max() if geom.wide else 0), (_lib.ptr(dt_scene),)
+    if geom.wide:
+        return stem + "_nv_f64", sizes + (geom.nvcap, geom.verts_max()), ()
+    return stem + "_f64", sizes, ()
+
+
 def move_and_find_contacts(geom, p_start, v, dt, maxc=16, eps=EPSILON, tol=TOL, strict=True, dt_floor=None,
                            max_trials=64, t=None, out=None, dt_scene=None, broadphase=False, candidates=None):
     """`p <- p_start + v dt`, contacts at the new pose, dt halving while a contact penetrates by more than `tol`
@@ -188,30 +218,14 @@ def move_and_find_contacts(geom, p_start, v, dt, maxc=16, eps=EPSILON, tol=TOL, 
     padded spheres of `bodies.py:_create_geom`) and only the survivors reach the narrow phase; the outputs are the same bit for bit.
     `candidates`: an optional [B] int32 device tensor that receives the number of surviving pairs at the accepted pose."""
     lib = _lib.load()
-    B, nb = geom.B, geom.nb
-    _lib.require_gpu_tensor(geom.kind, "kind", torch.int32)
-    _lib.require_gpu_tensor(geom.nverts, "nverts", torch.int32)
-    _lib.require_gpu_tensor(geom.radius, "radius", torch.float64)
-    _lib.require_gpu_tensor(geom.verts_local, "verts_local", torch.float64)
-    _lib.require_gpu_tensor(p_start, "p_start", torch.float64)
-    if (tuple(p_start.shape) != (B, nb, 3) or tuple(geom.verts_local.shape) != (B, nb, geom.nvcap, 2)
-            or not NV <= geom.nvcap <= NV_MAX):
-        raise RuntimeError("p_start must be [B,nb,3] and verts_local [B,nb,cap,2] with %d <= cap <= %d" % (NV, NV_MAX))
+    B, nb = _check_geometry(geom, p_start, "p_start")
     if v is not None:
         _lib.require_gpu_tensor(v, "v", torch.float32)
-    if geom.no_contact is not None:
-        _lib.require_gpu_tensor(geom.no_contact, "no_contact", torch.uint8)
     if t is not None:
         _lib.require_gpu_tensor(t, "t", torch.float64)
     dev = p_start.device
     if out is None:
         out = ContactBuffers(B, nb, maxc, dev)
-    P = _lib.ptr
-    args = (P(geom.kind), P(geom.radius), P(geom.verts_local), P(geom.nverts), P(geom.no_contact),
-            P(p_start), P(v), float(dt), float(dt / 4 if dt_floor is None else dt_floor), int(bool(strict)),
-            int(max_trials), float(eps), float(tol), P(out.p_out), P(out.c_n), P(out.c_p1), P(out.c_p2),
-            P(out.c_pen), P(out.c_i1), P(out.c_i2), P(out.count), P(out.max_pen), P(out.dt_used), P(t),
-            P(out.trials))
     if dt_scene is not None:
         _lib.require_gpu_tensor(dt_scene, "dt_scene", torch.float64)
         if tuple(dt_scene.shape) != (B,):
@@ -222,27 +236,15 @@ def move_and_find_contacts(geom, p_start, v, dt, maxc=16, eps=EPSILON, tol=TOL, 
         _lib.require_gpu_tensor(candidates, "candidates", torch.int32)
         if tuple(candidates.shape) != (B,):
             raise RuntimeError("candidates must be [B]")
-    if broadphase:
-        with torch.cuda.device(dev):                                        # (the real vertex total, also for a batch that is not `wide`)
-            rc = lib.lcp_move_find_contacts_bp_f64(B, nb, out.maxc, geom.nvcap, geom.verts_max(), *args, P(dt_scene), P(candidates),
-                                                   _lib.stream_ptr(dev))
-        _lib.check(rc, "lcp_move_find_contacts_bp_f64")
-        return out
-    if dt_scene is not None:
-        with torch.cuda.device(dev):
-            rc = lib.lcp_move_find_contacts_dts_f64(B, nb, out.maxc, geom.nvcap, 0 if not geom.wide else geom.verts_max(), *args,
-                                                    P(dt_scene), _lib.stream_ptr(dev))
-        _lib.check(rc, "lcp_move_find_contacts_dts_f64")
-        return out
-    args += (_lib.stream_ptr(dev),)
-    if geom.wide:
-        with torch.cuda.device(dev):
-            rc = lib.lcp_move_find_contacts_nv_f64(B, nb, out.maxc, geom.nvcap, geom.verts_max(), *args)
-        _lib.check(rc, "lcp_move_find_contacts_nv_f64")
-        return out
+    P = _lib.ptr
+    name, sizes, tail = _entry(geom, "lcp_move_find_contacts", (B, nb, out.maxc), dt_scene, broadphase, candidates)
     with torch.cuda.device(dev):
-        rc = lib.lcp_move_find_contacts_f64(B, nb, out.maxc, *args)
-    _lib.check(rc, "lcp_move_find_contacts_f64")
+        rc = getattr(lib, name)(*sizes, P(geom.kind), P(geom.radius), P(geom.verts_local), P(geom.nverts), P(geom.no_contact),
+                                P(p_start), P(v), float(dt), float(dt / 4 if dt_floor is None else dt_floor), int(bool(strict)),
+                                int(max_trials), float(eps), float(tol), P(out.p_out), P(out.c_n), P(out.c_p1), P(out.c_p2),
+                                P(out.c_pen), P(out.c_i1), P(out.c_i2), P(out.count), P(out.max_pen), P(out.dt_used), P(t),
+                                P(out.trials), *tail, _lib.stream_ptr(dev))
+    _lib.check(rc, name)
     return out
 
 
@@ -253,32 +255,28 @@ def find_contacts(geom, p, maxc=16, eps=EPSILON, out=None, broadphase=False, can
                                   candidates=candidates)
 
 
+def _check_cotangents(g_n, g_p1, g_p2):
+    for name, t in (("g_n", g_n), ("g_p1", g_p1), ("g_p2", g_p2)):
+        _lib.require_gpu_tensor(t, name, torch.float32)
+
+
 def contact_frame_backward(geom, p, cb, g_n, g_p1, g_p2, eps=EPSILON):
     """d(loss)/d(pose) through the contact frame (`lcp_contact_frame_backward_f64`): the chain rule of the reference's
     differentiable contact handler (`contacts.py:57-352`) for the contacts in `cb` detected at pose `p` [B,nb,3] float64 with
     margin `eps` - every record type (circle / circle, circle / hull, hull / hull).  `cb`: the records (`ContactBuffers` or
     a snapshot: c_n, c_i1, c_i2, count)."""
     lib = _lib.load()
-    B, nb = geom.B, geom.nb
+    B, nb = _check_geometry(geom, p, "p")
+    _check_cotangents(g_n, g_p1, g_p2)
     dev = p.device
-    for name, t in (("g_n", g_n), ("g_p1", g_p1), ("g_p2", g_p2)):
-        _lib.require_gpu_tensor(t, name, torch.float32)
-    _lib.require_gpu_tensor(p, "p", torch.float64)
     dp = torch.empty(B, nb, 3, dtype=torch.float64, device=dev)
     P = _lib.ptr
-    if geom.wide:
-        with torch.cuda.device(dev):
-            rc = lib.lcp_contact_frame_backward_nv_f64(B, nb, cb.c_n.shape[1], geom.nvcap, geom.verts_max(), P(geom.kind),
-                                                       P(geom.radius), P(geom.verts_local), P(geom.nverts), P(geom.no_contact),
-                                                       P(p), float(eps), P(cb.count), P(cb.c_i1), P(cb.c_i2), P(g_n), P(g_p1),
-                                                       P(g_p2), P(dp), _lib.stream_ptr(dev))
-        _lib.check(rc, "lcp_contact_frame_backward_nv_f64")
-        return dp
+    name, sizes, _ = _entry(geom, "lcp_contact_frame_backward", (B, nb, cb.c_n.shape[1]))
+    pairs = (P(cb.c_i1), P(cb.c_i2)) if geom.wide else ()               # (the _nv_ entry reads the pairs from the records)
     with torch.cuda.device(dev):
-        rc = lib.lcp_contact_frame_backward_f64(B, nb, cb.c_n.shape[1], P(geom.kind), P(geom.radius), P(geom.verts_local),
-                                                P(geom.nverts), P(geom.no_contact), P(p), float(eps), P(cb.count), P(g_n), P(g_p1),
-                                                P(g_p2), P(dp), _lib.stream_ptr(dev))
-    _lib.check(rc, "lcp_contact_frame_backward_f64")
+        rc = getattr(lib, name)(*sizes, P(geom.kind), P(geom.radius), P(geom.verts_local), P(geom.nverts), P(geom.no_contact), P(p),
+                                float(eps), P(cb.count), *pairs, P(g_n), P(g_p1), P(g_p2), P(dp), _lib.stream_ptr(dev))
+    _lib.check(rc, name)
     return dp
 
 
@@ -290,21 +288,16 @@ def contact_frame_backward_shape(geom, p, cb, g_n, g_p1, g_p2, eps=EPSILON, want
     Circles get zero vertex gradient, hulls zero radius gradient, vertex slots beyond `nverts` zero.  An output that is not
     wanted is None."""
     lib = _lib.load()
-    B, nb = geom.B, geom.nb
+    B, nb = _check_geometry(geom, p, "p")
+    _check_cotangents(g_n, g_p1, g_p2)
     dev = p.device
-    for name, t in (("g_n", g_n), ("g_p1", g_p1), ("g_p2", g_p2)):
-        _lib.require_gpu_tensor(t, name, torch.float32)
-    _lib.require_gpu_tensor(p, "p", torch.float64)
-    radius, verts = geom.radius.detach(), geom.verts_local.detach()
-    _lib.require_gpu_tensor(radius, "radius", torch.float64)
-    _lib.require_gpu_tensor(verts, "verts_local", torch.float64)
     d_rad = torch.empty(B, nb, dtype=torch.float64, device=dev) if want_radius else None
     d_verts = torch.empty(B, nb, geom.nvcap, 2, dtype=torch.float64, device=dev) if want_verts else None
     P = _lib.ptr
     with torch.cuda.device(dev):
-        rc = lib.lcp_contact_frame_backward_shape_f64(B, nb, cb.c_n.shape[1], geom.nvcap, geom.verts_max(), P(geom.kind), P(radius),
-                                                      P(verts), P(geom.nverts), P(p), float(eps), P(cb.count), P(cb.c_i1), P(cb.c_i2),
-                                                      P(g_n), P(g_p1), P(g_p2), P(d_rad), P(d_verts), _lib.stream_ptr(dev))
+        rc = lib.lcp_contact_frame_backward_shape_f64(B, nb, cb.c_n.shape[1], geom.nvcap, geom.verts_max(), P(geom.kind), P(geom.radius),
+                                                      P(geom.verts_local), P(geom.nverts), P(p), float(eps), P(cb.count), P(cb.c_i1),
+                                                      P(cb.c_i2), P(g_n), P(g_p1), P(g_p2), P(d_rad), P(d_verts), _lib.stream_ptr(dev))
     _lib.check(rc, "lcp_contact_frame_backward_shape_f64")
     return d_rad, d_verts
 

@@ -44,35 +44,64 @@ def test_signature_matches_the_header():
     assert "world.py:139-142" in doc and "bodies.py:_create_geom" in doc and "bitwise" in doc
 
 
+# the four detection entries: has the entry the (nvcap, scene_verts_max) arguments, a dt_scene, a candidates argument ?
+ENTRIES = {"lcp_move_find_contacts_f64": (False, False, False), "lcp_move_find_contacts_nv_f64": (True, False, False),
+           "lcp_move_find_contacts_dts_f64": (True, True, False), NAME: (True, True, True)}
+BADARG, TOOLARGE, ACCEPTED = -1, -2, -3      # ACCEPTED: the checks passed; without a GPU the launch itself fails (LCP_E_LAUNCH)
+
+
 def test_sizes_and_required_pointers_are_checked_before_any_launch():
-    """The argument and size errors of the _nv_ entry, with stand-in pointers: every case returns before a launch.  Only where no GPU
-    is present, so that a regression of these checks cannot launch a kernel on such addresses; tests/test_hip_broadphase.py repeats the
-    cases with device buffers."""
+    """The argument and size errors of the four detection entries, with stand-in pointers: every refusal returns before a launch,
+    LCP_E_BADARG before LCP_E_TOOLARGE, and the sizes at the edge of each entry's limits are accepted.  Only where no GPU is present, so
+    that a regression of these checks cannot launch a kernel on such addresses (an accepted call then fails at the launch and reads no
+    pointer); tests/test_hip_broadphase.py repeats the cases of the _bp_ entry with device buffers."""
     import torch
     from lcp_physics_amd import _lib
     if torch.cuda.is_available():
         pytest.skip("GPU present: tests/test_hip_broadphase.py checks these cases with device buffers")
     lib = _lib.load()
+    for name in ENTRIES:
+        _check_refusals(lib, name)
+
+
+def _check_refusals(lib, name):
+    sized, has_dts, has_cand = ENTRIES[name]
+    small = not sized                                                        # lcp_contacts.hip alone: 8 vertices, 32 bodies
     fake = lambda n: [ctypes.c_void_p(0x1000 * (k + 1)) for k in range(n)]
 
-    def call(nb=12, nvcap=16, vmax=64, B=4, maxc=16, trials=8, geo=None, outs=None):
+    def call(nb=12, nvcap=16, vmax=64, B=4, maxc=16, trials=8, geo=None, outs=None, dt_scene=ctypes.c_void_p(0xa000)):
         geo = fake(4) if geo is None else geo
         outs = fake(12) if outs is None else outs
-        return getattr(lib, NAME)(B, nb, maxc, nvcap, vmax, *geo, None, ctypes.c_void_p(0x9000), None, 1.0 / 30, 1.0 / 120, 1, trials, 0.1,
-                                  1e-6, *outs, None, None, None)
+        sizes = (B, nb, maxc) + ((nvcap, vmax) if sized else ())
+        tail = ((dt_scene,) if has_dts else ()) + ((None,) if has_cand else ()) + (None,)      # .., candidates, stream
+        return getattr(lib, name)(*sizes, *geo, None, ctypes.c_void_p(0x9000), None, 1.0 / 30, 1.0 / 120, 1, trials, 0.1, 1e-6, *outs,
+                                  *tail)
 
-    for kw in (dict(nb=65), dict(nvcap=7), dict(nvcap=65), dict(vmax=1025)):
-        assert call(**kw) == -2, kw                                          # LCP_E_TOOLARGE
-    for kw in (dict(B=0), dict(nb=0), dict(maxc=0), dict(trials=0), dict(vmax=-1)):
-        assert call(**kw) == -1, kw                                          # LCP_E_BADARG
-    for k in range(4):
+    assert call(nb=33) == (TOOLARGE if small else ACCEPTED), name
+    assert call(nb=65) == TOOLARGE
+    if sized:
+        for kw in (dict(nvcap=7), dict(nvcap=65), dict(vmax=1025)):
+            assert call(**kw) == TOOLARGE, kw
+        assert call(vmax=-1) == BADARG
+    for kw in (dict(B=0), dict(nb=0), dict(maxc=0), dict(trials=0)):
+        assert call(**kw) == BADARG, kw
+    assert call(nb=65, vmax=-1) == (TOOLARGE if small else BADARG)           # (no scene_verts_max argument: the size alone)
+    if has_dts:
+        assert call(dt_scene=None) == (ACCEPTED if has_cand else BADARG)     # (_bp_: NULL = the scalar dt)
+    for k in range(4):                                                       # kind radius verts_local nverts
         geo = fake(4)
         geo[k] = None
-        assert call(geo=geo) == -1, k
+        assert call(geo=geo) == BADARG, k
+        if k == 0:
+            assert call(nb=65, geo=geo) == BADARG
     for k in (1, 2, 3, 5, 6, 7):                                             # c_n c_p1 c_p2 c_i1 c_i2 count
         outs = fake(12)
         outs[k] = None
-        assert call(outs=outs) == -1, k
+        assert call(outs=outs) == BADARG, k
+    accepted = [dict(), dict(nb=32)] if small else [dict(), dict(nb=64, nvcap=8), dict(nb=32, nvcap=8), dict(nvcap=64), dict(vmax=0),
+                                                    dict(vmax=1024)]
+    for kw in accepted:
+        assert call(**kw) == ACCEPTED, kw
 
 
 def _shape(kind, size):

@@ -74,7 +74,14 @@ def test_per_scene_dt_matches_the_oracle_scene_by_scene(nb, B, maxc, strict):
     assert int(cb.trials.max()) > 1                                      # somebody halved
 
 
-@pytest.mark.parametrize("nb,B,maxc", SIZES, ids=["nb3-quad-wave", "nb7-one-wave", "nb33-wide"])
+# the last and the first body count on either side of an instantiation of lcp_move_find_contacts_kernel: <16, 6> up to 6 bodies,
+# <64, 16> up to 16, <64, MAXB> for 17 .. 32 (33 bodies: the wide kernel, above)
+EDGE_SIZES = [(6, 5, 32), (16, 3, 96), (17, 3, 96), (32, 3, 160)]
+
+
+@pytest.mark.parametrize("nb,B,maxc", SIZES + EDGE_SIZES,
+                         ids=["nb3-quad-wave", "nb7-one-wave", "nb33-wide", "nb6-quad-wave-last", "nb16-one-wave-last", "nb17-maxb-first",
+                              "nb32-maxb-last"])
 def test_equal_per_scene_dts_are_bitwise_the_scalar_entry(nb, B, maxc):
     from lcp_physics_amd.physics.contacts import move_and_find_contacts
     scenes, p0, v32 = _thrown_scenes(nb, B)
@@ -86,6 +93,7 @@ def test_equal_per_scene_dts_are_bitwise_the_scalar_entry(nb, B, maxc):
         b = move_and_find_contacts(geom, p_start, v, DT, maxc=maxc, strict=strict, t=tb,
                                    dt_scene=torch.full((B,), DT, dtype=torch.float64, device=DEV))
         torch.cuda.synchronize()
+        assert int(a.count.max()) <= maxc
         assert int(a.trials.max()) > 1
         assert _bits(ta, tb) and _bits(a.p_out, b.p_out)
         for n in RECORDS:
