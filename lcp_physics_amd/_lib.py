@@ -3,6 +3,7 @@
 There is deliberately no fallback: if the shared library is missing or a call fails, the
 caller gets an exception.  PyTorch is only used for device memory and streams.
 """
+import contextlib
 import ctypes
 import os
 import threading
@@ -120,6 +121,13 @@ def ptr(t):
 
 def stream_ptr(device):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def on_device(dev):
+    """`with torch.cuda.device(dev)` costs several microseconds per call: entered only when `dev` is not already current."""
+    if dev.index is None or torch.cuda.current_device() == dev.index:
+        return contextlib.nullcontext()
+    return torch.cuda.device(dev)
 
 
 def require_gpu_tensor(t, name, dtype=None):

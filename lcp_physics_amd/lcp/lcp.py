@@ -122,8 +122,7 @@ def lcp_backward(sol, dl_dx, need=(True,) * 7, out=None, adjoint=False):
         raise ValueError("lcp_backward(adjoint=True) needs a solution of lcp_solve(..., path='generic')")
     if (plan is not None and out is not None and plan[0] is out and dl_dx.dtype == dtype and dl_dx.is_contiguous()
             and plan[1] == _bwd_key(sol, dl_dx, out) and not adjoint):
-        from ..physics.batched_world import _on_device
-        with _on_device(dev):
+        with _lib.on_device(dev):
             rc = plan[2](*plan[3], _lib.stream_ptr(dev))
         _lib.check(rc, "lcp_pdipm_backward")
         return out

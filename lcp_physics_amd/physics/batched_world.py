@@ -14,7 +14,8 @@ import torch
 
 from .. import _lib
 from ..lcp.lcp import _COMPUTE, LCPSolution
-from ..scenes import SceneBatch
+from ..scenes import SceneBatch, eq_rows
+from .dense_step import post_stabilization_dense, require_fused_record, solve_dynamics_dense
 
 
 def scene_from_contacts(p, v, Mdiag, f, rest, fric, contacts, Je, dt):
@@ -34,7 +35,7 @@ def _check_scene(sc):
         _lib.require_gpu_tensor(getattr(sc, name), name, torch.float32)
     _lib.require_gpu_tensor(sc.c_i1, "c_i1", torch.int32)
     _lib.require_gpu_tensor(sc.c_i2, "c_i2", torch.int32)
-    e = sc.Je.shape[1] if sc.Je is not None and sc.Je.numel() else 0
+    e = eq_rows(sc.Je)
     if e:
         _lib.require_gpu_tensor(sc.Je, "Je", torch.float32)
     return e
@@ -52,7 +53,7 @@ def assemble_contacts(sc):
     Q, p, G, h, F = new(B, nz, nz), new(B, nz), new(B, m, nz), new(B, m), new(B, m, m)
     A, b = (new(B, e, nz), new(B, e)) if e else (None, None)
     P = _lib.ptr
-    with _on_device(dev):
+    with _lib.on_device(dev):
         rc = lib.lcp_assemble_contacts_f32(B, nb, nc, e, P(sc.Mdiag), P(sc.v), P(sc.f), P(sc.rest),
                                            P(sc.fric), P(sc.c_n), P(sc.c_p1), P(sc.c_p2), P(sc.c_i1),
                                            P(sc.c_i2), P(sc.Je) if e else None, float(sc.dt),
@@ -64,9 +65,10 @@ def assemble_contacts(sc):
 def rows_pin_leading_coordinates(Je):
     """Host check (synchronises once): every scene's equality rows are Je = [I 0] - the TotalConstraint that fixes the floor of
     the reference's demo worlds (`constraints.py:175-192`) -, or there are none.  What `LCP_HINT_PINNED` promises."""
-    if Je is None or Je.numel() == 0:
+    e = eq_rows(Je)
+    if not e:
         return True
-    e, nz = Je.shape[1], Je.shape[2]
+    nz = Je.shape[2]
     if e > nz:
         return False
     eye = torch.zeros(e, nz, dtype=Je.dtype, device=Je.device)
@@ -87,17 +89,15 @@ def _pinned_hint(sc, pinned):
     return _lib.HINT_PINNED if pinned else 0
 
 
-def _on_device(dev):
-    """`with torch.cuda.device(dev)` costs several microseconds per call: entered only when `dev` is not already current."""
-    import contextlib
-    if dev.index is None or torch.cuda.current_device() == dev.index:
-        return contextlib.nullcontext()
-    return torch.cuda.device(dev)
-
-
 _SCENE_FIELDS = ("p", "Mdiag", "v", "f", "rest", "fric", "c_n", "c_p1", "c_p2", "c_i1", "c_i2")
 _STEP_OUTPUTS = ("v_new", "p_new", "z", "s", "y", "iters", "status")
 _STEP_KEY_LEN = 10                       # entries of fused_step's plan key before the output pointers
+
+
+def _output_ptrs(out):
+    """The tail of `fused_step`'s plan key: where the step writes - every output tensor of `out` (0: not written) and its workspace."""
+    return (tuple(0 if out.get(k) is None else out[k].data_ptr() for k in _STEP_OUTPUTS),
+            0 if out.get("ws") is None else out["ws"].data_ptr())
 
 
 def fused_step(sc, eps=1e-12, not_improved_lim=3, max_iter=10, compute="f64", ws=None, out=None, path="auto", pinned=None,
@@ -120,11 +120,10 @@ def fused_step(sc, eps=1e-12, not_improved_lim=3, max_iter=10, compute="f64", ws
     if out is not None:
         # ... and on the OUTPUT tensors the caller hands back: an entry of `out` that was replaced (to keep the old result) or a
         # different workspace gets a fresh argument list, never a write through a stale pointer
-        key += (tuple(0 if out.get(k) is None else out[k].data_ptr() for k in _STEP_OUTPUTS),
-                0 if out.get("ws") is None else out["ws"].data_ptr())
+        key += _output_ptrs(out)
     plan = None if out is None else out.get("_plan")
     if plan is not None and plan[0] == key and (ws is None or ws is out["ws"]):
-        with _on_device(dev):
+        with _lib.on_device(dev):
             rc = lib.lcp_step_fused_f32(*plan[1], _lib.stream_ptr(dev))
         _lib.check(rc, "lcp_step_fused_f32")
         return out
@@ -147,11 +146,11 @@ def fused_step(sc, eps=1e-12, not_improved_lim=3, max_iter=10, compute="f64", ws
     args = (B, nb, nc, e, P(sc.p), P(sc.Mdiag), P(sc.v), P(sc.f), P(sc.rest), P(sc.fric), P(sc.c_n), P(sc.c_p1), P(sc.c_p2),
             P(sc.c_i1), P(sc.c_i2), P(sc.Je) if e else None, float(sc.dt), float(eps), int(max_iter), int(not_improved_lim), comp,
             P(out["v_new"]), P(out["p_new"]), P(out["z"]), P(out["s"]), P(out["y"]), P(out["iters"]), P(out["status"]), P(ws))
-    with _on_device(dev):
+    with _lib.on_device(dev):
         rc = lib.lcp_step_fused_f32(*args, _lib.stream_ptr(dev))
     _lib.check(rc, "lcp_step_fused_f32")
     out["compute"] = comp                 # the word the backward must carry: arithmetic + kernel path (a family per word, any thread)
-    key = key[:_STEP_KEY_LEN] + (tuple(0 if out.get(k) is None else out[k].data_ptr() for k in _STEP_OUTPUTS), ws.data_ptr())
+    key = key[:_STEP_KEY_LEN] + _output_ptrs(out)
     out["_plan"] = (key, args)            # (valid while the scene, the options, the output tensors and the workspace are the same)
     return out
 
@@ -165,39 +164,18 @@ def fused_step_backward(sc, out, dl_dv, compute="f64", grads=None, want_Je=False
     """Backward of `fused_step` with respect to the physical inputs of the scenes: d(loss)/d(v_new) [B,nb,3] ->
     dict(Mdiag, v, f [B,nb,3], rest, fric [B,nb], c_n, c_p1, c_p2 [B,nc,2]) - what the reference computes by
     autograd through `engines.py:31-32,50-77` and `world.py:144-234` after `LCPFunction.backward`.  One launch of
-    `lcp_step_backward_je_f32`; the dense LCP gradients are never materialised.  `out` is the dict `fused_step`
-    returned (its workspace is read); the scene must not have changed in between.  `want_Je`: also "Je" [B,e,3nb], the
-    gradient of the joint Jacobian (`lcp.py:57`, dA = dnu x^T + nu dx^T)."""
-    lib = _lib.load()
-    from .dense_step import require_fused_record
+    `lcp_step_backward_je_f32` (`solve_dynamics_backward` with the scene as the holder of the contact records); the dense LCP
+    gradients are never materialised.  `out` is the dict `fused_step` returned (its workspace is read); the scene must not have
+    changed in between.  `want_Je`: also "Je" [B,e,3nb], the gradient of the joint Jacobian (`lcp.py:57`, dA = dnu x^T + nu dx^T)."""
     require_fused_record(out, "fused_step_backward")
     e = _check_scene(sc)
-    B, nb, nc = sc.B, sc.nb, sc.nc
-    dev = sc.v.device
-    dl_dv = _lib.require_gpu_tensor(dl_dv.to(torch.float32).contiguous(), "dl_dv", torch.float32)
-    if grads is None:
-        new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-        grads = {"Mdiag": new(B, nb, 3), "v": new(B, nb, 3), "f": new(B, nb, 3), "rest": new(B, nb), "fric": new(B, nb),
-                 "c_n": new(B, nc, 2), "c_p1": new(B, nc, 2), "c_p2": new(B, nc, 2)}
-    if want_Je and e and "Je" not in grads:
-        grads["Je"] = torch.empty(B, e, 3 * nb, dtype=torch.float32, device=dev)
-    P = _lib.ptr
-    with _on_device(dev):
-        rc = lib.lcp_step_backward_je_f32(B, nb, nc, e, P(sc.Mdiag), P(sc.v), P(sc.f), P(sc.rest), P(sc.fric), P(sc.c_n),
-                                          P(sc.c_p1), P(sc.c_p2), P(sc.c_i1), P(sc.c_i2), P(sc.Je) if e else None,
-                                          float(sc.dt), P(dl_dv), _word(out, compute),
-                                          P(grads["Mdiag"]), P(grads["v"]),
-                                          P(grads["f"]), P(grads["rest"]), P(grads["fric"]), P(grads["c_n"]),
-                                          P(grads["c_p1"]), P(grads["c_p2"]), P(grads["Je"]) if (want_Je and e) else None,
-                                          P(out["ws"]), _lib.stream_ptr(dev))
-    _lib.check(rc, "lcp_step_backward_je_f32")
-    return grads
+    return solve_dynamics_backward(sc.B, sc.nb, sc.nc, e, sc.Mdiag, sc.v, sc.f, sc.rest, sc.fric, sc, sc.Je, sc.dt, dl_dv, out,
+                                   compute=compute, grads=grads, want_Je=want_Je)
 
 
 def solution_of_step(sc, out, G, A, compute="f64"):
     """Wrap a fused step's workspace as an `LCPSolution` so `lcp.lcp_backward` can follow
     (G, A from `assemble_contacts`)."""
-    from .dense_step import require_fused_record
     require_fused_record(out, "solution_of_step")
     sol = LCPSolution()
     B, nb, nc = sc.B, sc.nb, sc.nc
@@ -242,7 +220,7 @@ class BatchedWorld:
         if self._count is None or self._count.shape[0] != sc.B:
             self._count = torch.full((sc.B,), sc.nc, dtype=torch.int32, device=sc.v.device)
         opts = {"max_iter": self.max_iter, "eps": self.eps, "not_improved_lim": self.lim, "compute": self.compute}
-        e = sc.Je.shape[1] if sc.Je is not None and sc.Je.numel() else 0
+        e = eq_rows(sc.Je)
         v_new = SolveDynamicsFunction.apply(sc.Mdiag, sc.v, sc.f, sc.rest, sc.fric, sc.c_n, sc.c_p1, sc.c_p2, sc.c_i1,
                                             sc.c_i2, self._count, sc.Je if e else None, sc.dt, opts)
         p_new = sc.p + v_new * sc.dt
@@ -307,7 +285,7 @@ def solve_dynamics(B, nb, maxc, e, count, Mdiag, v, f, rest, fric, cb, Je, dt, e
                "status": torch.empty(B, dtype=torch.int32, device=dev)}
     out["ws"] = ws
     P = _lib.ptr
-    with _on_device(dev):
+    with _lib.on_device(dev):
         rc = lib.lcp_solve_dynamics_f32(B, nb, maxc, e, P(count), P(Mdiag), P(v), P(f), P(rest), P(fric),
                                         P(cb.c_n), P(cb.c_p1), P(cb.c_p2), P(cb.c_i1), P(cb.c_i2),
                                         P(Je) if e else None, float(dt), float(eps), int(max_iter),
@@ -326,7 +304,6 @@ def solve_dynamics_backward(B, nb, maxc, e, Mdiag, v, f, rest, fric, cb, Je, dt,
     Returns dict(Mdiag, v, f [B,nb,3], rest, fric [B,nb], c_n, c_p1, c_p2 [B,maxc,2]) and, with `want_Je`, Je [B,e,3nb] - the
     gradient of the joint Jacobian (`lcp.py:57` with A = Je), which worlds with pose-dependent joints propagate on."""
     lib = _lib.load()
-    from .dense_step import require_fused_record
     require_fused_record(out, "solve_dynamics_backward")
     dev = v.device
     dl_dv = _lib.require_gpu_tensor(dl_dv.to(torch.float32).contiguous(), "dl_dv", torch.float32)
@@ -337,7 +314,7 @@ def solve_dynamics_backward(B, nb, maxc, e, Mdiag, v, f, rest, fric, cb, Je, dt,
     if want_Je and e and "Je" not in grads:
         grads["Je"] = torch.empty(B, e, 3 * nb, dtype=torch.float32, device=dev)
     P = _lib.ptr
-    with _on_device(dev):
+    with _lib.on_device(dev):
         rc = lib.lcp_step_backward_je_f32(B, nb, maxc, e, P(Mdiag), P(v), P(f), P(rest), P(fric), P(cb.c_n), P(cb.c_p1),
                                           P(cb.c_p2), P(cb.c_i1), P(cb.c_i2), P(Je) if e else None, float(dt), P(dl_dv),
                                           _word(out, compute),
@@ -366,7 +343,7 @@ def substep_begin(t, end_t, f, count, out=None):
         out = {"dt_k": torch.empty(B, dtype=torch.float64, device=dev), "active": torch.empty(B, dtype=torch.int32, device=dev),
                "count_eff": torch.empty(B, dtype=torch.int32, device=dev), "f_eff": torch.empty(B, nb, 3, dtype=torch.float32, device=dev)}
     P = _lib.ptr
-    with _on_device(dev):
+    with _lib.on_device(dev):
         rc = lib.lcp_substep_begin_f64(B, nb, P(t), P(end_t), P(f), P(count), P(out["dt_k"]), P(out["active"]), P(out["count_eff"]),
                                        P(out["f_eff"]), _lib.stream_ptr(dev))
     _lib.check(rc, "lcp_substep_begin_f64")
@@ -383,24 +360,24 @@ def substep_commit(active, v_old, v_new):
     B, nb = v_new.shape[0], v_new.shape[1]
     if tuple(v_new.shape) != (B, nb, 3) or v_old.shape != v_new.shape or tuple(active.shape) != (B,):
         raise RuntimeError("substep_commit: active must be [B], v_old and v_new [B,nb,3]")
-    with _on_device(v_new.device):
+    with _lib.on_device(v_new.device):
         rc = lib.lcp_substep_commit_f32(B, nb, _lib.ptr(active), _lib.ptr(v_old), _lib.ptr(v_new), _lib.stream_ptr(v_new.device))
     _lib.check(rc, "lcp_substep_commit_f32")
     return v_new
 
 
-class _ValueOf(torch.autograd.Function):
-    """y = `value` (bitwise: a copy of what the kernel computed) with the gradient of `lin`, the torch expression of the same
-    quantity.  `lin + (value - lin).detach()` can differ from `value` by an ulp - and the contact list of the next step was
-    detected at exactly `value` (a borderline pair must not change sides between the forward and the frame backward)."""
-
-    @staticmethod
-    def forward(ctx, lin, value):
-        return value.detach().clone()                 # (`value` may be a buffer the next launch overwrites)
-
-    @staticmethod
-    def backward(ctx, g):
-        return g, None
+def _apply_recorded(apply, args, v, c_n, Je, opts, query, dense):
+    """`apply(*args)` of `SolveDynamicsFunction` / `PostStabilizationFunction` - unless the call is being RECORDED at a size without
+    a fused backward.  Every kernel family keeps what its fused backward reads, the generic kernels (each scene's iterate and contact
+    count) included; only where `query(lib)` - the library's `lcp_step_has_backward` / `lcp_post_stabilization_has_backward` - answers
+    0 (the fp32 wave64 step family, sizes beyond the generic plan) does a recorded call go through the dense boundary instead, `dense`
+    (a function of physics/dense_step.py), the way the reference does at every size: decided here, when the step is recorded - not
+    with LCP_E_TOOLARGE in the middle of loss.backward().  (Inside forward() grad mode is off.)"""
+    if torch.is_grad_enabled() and any(isinstance(a, torch.Tensor) and a.requires_grad for a in args):
+        word = _COMPUTE[opts.get("compute", "f64")] | _lib.path_bits()
+        if not query(_lib.load())(v.shape[1], c_n.shape[1], eq_rows(Je), word):
+            return dense(*args)
+    return apply(*args)
 
 
 class _Frame:
@@ -445,7 +422,7 @@ class _StateUpdate(torch.autograd.Function):
         g_p, g_g, g_rot = c64(g_p), c64(g_g), (c64(g_rot) if js is not None else None)
         g_v = torch.empty(B, nb, 3, dtype=torch.float32, device=v.device)
         P = _lib.ptr
-        with _on_device(v.device):
+        with _lib.on_device(v.device):
             rc = lib.lcp_state_update_backward_f64(B, nb, 0 if g_rot is None else js.jtype.shape[1], P(g_p), P(g_g), P(g_rot), P(v), P(dt_used),
                                                    ctx.scale, P(js.jtype) if g_rot is not None else None,
                                                    P(js.jb1) if g_rot is not None else None, P(g_v), _lib.stream_ptr(v.device))
@@ -490,26 +467,17 @@ class SolveDynamicsFunction(torch.autograd.Function):
 
     @classmethod
     def apply(cls, Mdiag, v, f, rest, fric, c_n, c_p1, c_p2, c_i1, c_i2, count, Je, dt, opts):
-        # The generic kernels step any size forward but keep no iterate a fused backward could read.  A step that is being RECORDED at
-        # such a size goes through the dense boundary instead, the way the reference does at every size (physics/dense_step.py):
-        # decided here, when the step is recorded - not with LCP_E_TOOLARGE in the middle of loss.backward().  (Inside forward() grad
-        # mode is off.)
         if count is None:                                                  # (every scene uses all of its contact slots)
             count = torch.full((v.shape[0],), c_n.shape[1], dtype=torch.int32, device=v.device)
         args = (Mdiag, v, f, rest, fric, c_n, c_p1, c_p2, c_i1, c_i2, count, Je, dt, opts)
-        if torch.is_grad_enabled() and any(isinstance(a, torch.Tensor) and a.requires_grad for a in args):
-            nb, maxc = v.shape[1], c_n.shape[1]
-            e = 0 if Je is None or Je.numel() == 0 else Je.shape[1]
-            if not _lib.load().lcp_step_has_backward(nb, maxc, e, _COMPUTE[opts.get("compute", "f64")] | _lib.path_bits()):
-                from .dense_step import solve_dynamics_dense
-                return solve_dynamics_dense(*args)
-        return super(SolveDynamicsFunction, cls).apply(*args)
+        return _apply_recorded(super(SolveDynamicsFunction, cls).apply, args, v, c_n, Je, opts, lambda lib: lib.lcp_step_has_backward,
+                               solve_dynamics_dense)
 
     @staticmethod
     def forward(ctx, Mdiag, v, f, rest, fric, c_n, c_p1, c_p2, c_i1, c_i2, count, Je, dt, opts):
         B, nb = v.shape[0], v.shape[1]
         maxc = c_n.shape[1]
-        e = 0 if Je is None or Je.numel() == 0 else Je.shape[1]
+        e = eq_rows(Je)
         for name, t in (("Mdiag", Mdiag), ("v", v), ("f", f), ("rest", rest), ("fric", fric), ("c_n", c_n),
                         ("c_p1", c_p1), ("c_p2", c_p2)):
             _lib.require_gpu_tensor(t, name, torch.float32)
@@ -561,7 +529,7 @@ def post_stabilization(B, nb, maxc, e, count, Mdiag, v, rest, cb, Je, p=None, dt
         if t is not None:
             _lib.require_gpu_tensor(t, name, torch.float64)
     P = _lib.ptr
-    with _on_device(dev):
+    with _lib.on_device(dev):
         rc = lib.lcp_post_stabilization_f32(B, nb, maxc, e, P(count), P(Mdiag), P(v), P(rest), P(cb.c_n), P(cb.c_p1),
                                             P(cb.c_p2), P(cb.c_i1), P(cb.c_i2), P(Je) if e else None, float(eps),
                                             int(max_iter), int(not_improved_lim), comp, P(p), P(dt_scene), float(dt),
@@ -585,7 +553,7 @@ def post_stabilization_backward(B, nb, maxc, e, Mdiag, v, rest, cb, Je, dl_ddp, 
     if want_Je and e:
         grads["Je"] = new(B, e, 3 * nb)
     P = _lib.ptr
-    with _on_device(dev):
+    with _lib.on_device(dev):
         rc = lib.lcp_post_stabilization_backward_f32(B, nb, maxc, e, P(Mdiag), P(v), P(rest), P(cb.c_n), P(cb.c_p1), P(cb.c_p2),
                                                      P(cb.c_i1), P(cb.c_i2), P(Je) if e else None, P(dl_ddp), _word(out, compute),
                                                      P(grads["Mdiag"]), P(grads["v"]), P(grads["rest"]), P(grads["c_n"]),
@@ -602,23 +570,17 @@ class PostStabilizationFunction(torch.autograd.Function):
 
     @classmethod
     def apply(cls, Mdiag, v, rest, c_n, c_p1, c_p2, c_i1, c_i2, count, Je, opts):
-        # (as SolveDynamicsFunction.apply: a recorded correction of a size without a fused backward goes through the dense boundary)
         if count is None:
             count = torch.full((v.shape[0],), c_n.shape[1], dtype=torch.int32, device=v.device)
         args = (Mdiag, v, rest, c_n, c_p1, c_p2, c_i1, c_i2, count, Je, opts)
-        if torch.is_grad_enabled() and any(isinstance(a, torch.Tensor) and a.requires_grad for a in args):
-            nb, maxc = v.shape[1], c_n.shape[1]
-            e = 0 if Je is None or Je.numel() == 0 else Je.shape[1]
-            if not _lib.load().lcp_post_stabilization_has_backward(nb, maxc, e, _COMPUTE[opts.get("compute", "f64")] | _lib.path_bits()):
-                from .dense_step import post_stabilization_dense
-                return post_stabilization_dense(*args)
-        return super(PostStabilizationFunction, cls).apply(*args)
+        return _apply_recorded(super(PostStabilizationFunction, cls).apply, args, v, c_n, Je, opts,
+                               lambda lib: lib.lcp_post_stabilization_has_backward, post_stabilization_dense)
 
     @staticmethod
     def forward(ctx, Mdiag, v, rest, c_n, c_p1, c_p2, c_i1, c_i2, count, Je, opts):
         B, nb = v.shape[0], v.shape[1]
         maxc = c_n.shape[1]
-        e = 0 if Je is None or Je.numel() == 0 else Je.shape[1]
+        e = eq_rows(Je)
         for name, t in (("Mdiag", Mdiag), ("v", v), ("rest", rest), ("c_n", c_n), ("c_p1", c_p1), ("c_p2", c_p2)):
             _lib.require_gpu_tensor(t, name, torch.float32)
         frame = _Frame(c_n, c_p1, c_p2, c_i1, c_i2)
@@ -660,9 +622,10 @@ class ContactWorld:
     (Total/X/Y/Rot constraints) or a `JointSet` (revolute / fixed joints, Jacobian rebuilt every step and differentiated);
     up to 64 bodies per scene and hulls of up to 64 vertices (`GeometryBatch.from_shapes(..., max_verts=...)`), 1024 hull
     vertices per scene (beyond 32 bodies or 8 vertices per hull the detection runs on lcp_contacts_wide.hip).  Scenes with
-    3 nb <= 32, maxc <= 16, e <= 4 run on the four-scenes-per-wave solver, up to 64 contacts and 24 equality rows (3 nb + e <= 56) on the wave-per-scene body-space solver (both with a fused backward),
-    anything else on the generic kernels; a differentiable step of such a size goes through the dense boundary
-    (physics/dense_step.py: torch assembly on the device + `LCPFunction`, the reference's own route).
+    3 nb <= 32, maxc <= 16, e <= 4 run on the four-scenes-per-wave solver, up to 64 contacts and 24 equality rows (3 nb + e <= 56) on the wave-per-scene body-space solver,
+    larger ones on the workgroup-per-scene body-space kernels and anything else on the generic kernels - each with a fused backward.  A
+    differentiable step goes through the dense boundary (physics/dense_step.py: torch assembly on the device + `LCPFunction`, the
+    reference's own route) only at the sizes for which `lcp_step_has_backward` / `lcp_post_stabilization_has_backward` answer 0.
     `step(fixed_dt=True)` is the reference's fixed-interval mode (world.py:72-80): every scene repeats `step_dt(end_t - t)` until
     its clock reaches `t + dt`, so a roll-out of N steps leaves EVERY scene at `N dt` however often the penetration test halved.
     `post_stab=True` (off by default, as in the reference: utils.py:30) adds the two launches of world.py:109-121 to a
@@ -683,7 +646,12 @@ class ContactWorld:
         self.force_fn = force_fn
         self._ps_out = self._ps_ws = None
         self._Je_spare = None
-        self._phase, self._graphs, self._graphs_fixed = 0, {}, {}
+        self._drop_graphs()
+        # what differentiable steps leave behind (a fresh world has taken none): `_autograd_owned` - the state tensors are outputs of
+        # an autograd graph; `_p_geom` / `_jrot_ad` - the pose the geometry is differentiated at and the revolute joints' angles as
+        # graph tensors, each valid only while `self.p` is still the tensor named by `_p_geom_src` / `_jrot_src`
+        self._autograd_owned = False
+        self._p_geom = self._p_geom_src = self._jrot_ad = self._jrot_src = None
         self._contacts_mod = _contacts
         self.geom = geom
         dev = p.device
@@ -702,7 +670,7 @@ class ContactWorld:
             self.Je = joints.jacobian(self.p)
             self._jrot0 = joints.jrot1.clone()                              # (for `restart`)
         else:
-            self.e = 0 if Je is None or Je.numel() == 0 else Je.shape[1]
+            self.e = eq_rows(Je)
             self.Je = f32(Je) if self.e else None
         # a constant Je that pins the leading coordinates (the fixed floor of the demo worlds) or no Je at all: LCP_HINT_PINNED,
         # checked once here on the host
@@ -747,8 +715,10 @@ class ContactWorld:
         self.t.fill_(float(t))
         self.behind.zero_()
         self.sticky_status.zero_()              # (a device op: an overflow of an earlier roll-out must not fail this one's check)
-        self._p_geom_src = self._jrot_src = None
-        self._graphs, self._graphs_fixed, self._phase = {}, {}, 0
+        # nothing of the recorded steps before describes the new pose (`_autograd_owned` stays as it is: a world that has recorded steps
+        # goes on copying its state before the next plain step - one copy too many at the worst)
+        self._p_geom = self._p_geom_src = self._jrot_ad = self._jrot_src = None
+        self._drop_graphs()
         pd = self.p.detach()
         if self.joints is not None:
             self.joints.jrot1.copy_(self._jrot0 if jrot1 is None else jrot1)
@@ -789,53 +759,32 @@ class ContactWorld:
         host then issues one graph launch per two simulation steps instead of 2-4 kernel launches with their Python
         marshalling per step - what bounds small batches.  Same kernels, same order, same results.
         `fixed_dt` / `max_substeps`: as in `step()`; a graph needs a launch sequence that does not depend on the data, so `graph=True`
-        with `fixed_dt` requires `max_substeps` (`behind` is checked once at the end)."""
+        with `fixed_dt` requires `max_substeps` (`behind` is checked once at the end).  Both modes share the loop below and the cache
+        `_graphs`, keyed on the buffer parity and on `max_substeps` (None: plain steps)."""
         if fixed_dt and graph and max_substeps is None:
             raise ValueError("run(graph=True, fixed_dt=True) needs max_substeps: the synchronising loop cannot be captured")
         if not fixed_dt and max_substeps is not None:
             raise ValueError("max_substeps belongs to fixed_dt=True")
-        if fixed_dt:
-            return self._run_fixed(nsteps, graph, max_substeps)
+        if max_substeps is not None:
+            max_substeps = int(max_substeps)
+        step = (lambda: self.step(fixed_dt=True, max_substeps=max_substeps)) if fixed_dt else self.step
         k = 0
         if graph and nsteps >= 2:
-            while not self._graphs and k < 2:
-                self.step()                                                # warm-up: every buffer exists before capture
-                k += 1
-            g = self._graphs.get(self._phase)
-            if g is None and nsteps - k >= 2:
-                torch.cuda.synchronize(self.p.device)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self.step()
-                    self.step()
-                self._graphs[self._phase] = g                              # (capture only records: nothing has run)
-            while g is not None and nsteps - k >= 2:
-                g.replay()
-                k += 2
-        while k < nsteps:
-            self.step()
-            k += 1
-        if self.check:
-            self.assert_not_truncated()                                    # one synchronisation per run, none per step
-
-    def _run_fixed(self, nsteps, graph, max_substeps):
-        """`run()` in the fixed-interval mode.  The graphs of this mode (two steps of `max_substeps` sub-steps each) are kept apart
-        from the plain ones (`_graphs_fixed`): keyed on the buffer parity AND the sub-step count."""
-        step = lambda: self.step(fixed_dt=True, max_substeps=max_substeps)
-        k = 0
-        if graph and nsteps >= 2:
-            key = (self._phase, int(max_substeps))                # (two steps flip the buffers an even number of times)
-            g = self._graphs_fixed.get(key)
-            while g is None and k < 2:
-                step()                                                     # warm-up: every buffer exists before capture
-                k += 1
+            # warm-up: every buffer exists before capture.  A graph of the same mode in the cache - plain, or fixed-interval with ANY
+            # sub-step count (`_sub`, `_end_t`, `_out`, `_ws` exist after one fixed-interval step whatever K) - says that they do.
+            if not any((K is None) == (max_substeps is None) for _, K in self._graphs):
+                step()
+                step()
+                k = 2
+            key = (self._phase, max_substeps)                              # (two steps flip the buffers an even number of times)
+            g = self._graphs.get(key)
             if g is None and nsteps - k >= 2:
                 torch.cuda.synchronize(self.p.device)
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
                     step()
                     step()
-                self._graphs_fixed[key] = g                                      # (capture only records: nothing has run)
+                self._graphs[key] = g                                      # (capture only records: nothing has run)
             while g is not None and nsteps - k >= 2:
                 g.replay()
                 k += 2
@@ -846,6 +795,11 @@ class ContactWorld:
             self.assert_not_truncated()                                    # one synchronisation per run, none per step
             if max_substeps is not None:
                 self.assert_on_schedule()
+
+    def _drop_graphs(self):
+        """Forget every captured graph.  They hold raw pointers: whoever retires or replaces a buffer the steps write through calls
+        this, or a later replay writes through the old pointers."""
+        self._graphs, self._phase = {}, 0      # (phase, max_substeps) -> two captured steps; max_substeps None: plain steps
 
     def step_autograd(self, _end_t=None):
         """`step()` as a node of torch's autograd graph, for losses evaluated after a roll-out (`demos/grad_demo.py:45-50`,
@@ -870,18 +824,18 @@ class ContactWorld:
         self._autograd_owned = True
         # HIP graphs captured by an earlier run(graph=True) hold raw pointers to the buffers retired here (they now belong to this
         # step's backward) and to the old state tensors: a later run() must capture again on the new ones
-        self._graphs, self._graphs_fixed, self._phase = {}, {}, 0
+        self._drop_graphs()
         # the pose the GEOMETRY is differentiated at: the same values as self.p, but a rotation increment that is exactly
         # zero carries no gradient - the reference turns its hulls' vertices by the increment and skips the turn when the
         # increment is zero (bodies.py:199-202 `if rot.item() != 0: self.rotate_verts(rot)`), so its autograd has no
         # vertex path through such a step (a hull in free fall with no torque on it, for instance)
-        p_geo = self._p_geom if getattr(self, "_p_geom_src", None) is self.p else self.p
+        p_geo = self._p_geom if self._p_geom_src is self.p else self.p
         # the shape as an input of the frame nodes where it requires grad (lcp_contact_frame_backward_shape_f64); the detection
         # launches read its values through raw pointers either way
         shape_in = tuple(t if t.requires_grad else None for t in (self.geom.radius, self.geom.verts_local))
         shape_in = shape_in if any(t is not None for t in shape_in) else ()
         c_n, c_p1, c_p2 = ct.ContactFrameFunction.apply(p_geo, self.geom, frame, self.eps, *shape_in)
-        f = self.f if self.force_fn is None else self.force_fn(self.t).to(torch.float32).contiguous()
+        f = self._forces()
         count, dt_solve, sub = frame.count, self.dt, None
         if _end_t is not None:
             # u = M v + dt_k f(t) (engines.py:31-32) as the solve with dt = 1 and f_eff = float(dt_k) * f: the same fp32 value, and the
@@ -897,7 +851,7 @@ class ContactWorld:
         if js is not None and js.pose_dependent:
             # the joint Jacobian as a function of the pose and of the revolute joints' angles (constraints.py:26-50): the
             # kernel's values, the gradient of the torch expression; lcp_step_backward_je_f32 returns dL/dJe
-            if getattr(self, "_jrot_src", None) is not self.p:
+            if self._jrot_src is not self.p:
                 self._jrot_ad, self._jrot_src = js.jrot1.clone(), self.p
             Je = _JointJacobianFn.apply(self.p, self._jrot_ad, js.jr1, js, self.Je)
         v_new = SolveDynamicsFunction.apply(self.Mdiag, self.v.contiguous(), f, self.rest, self.fric, c_n, c_p1, c_p2, frame.c_i1,
@@ -907,21 +861,14 @@ class ContactWorld:
             self.substeps += sub["active"]
         out = opts["last"]
         torch.bitwise_or(self.sticky_status, out["status"], out=self.sticky_status)
-        p_start = self.p
-        ct.move_and_find_contacts(self.geom, p_start.detach(), v_new.detach(), self.dt, eps=self.eps, tol=self.tol,
+        ct.move_and_find_contacts(self.geom, self.p.detach(), v_new.detach(), self.dt, eps=self.eps, tol=self.tol,
                                   strict=self.strict, dt_floor=self.dt / 4, max_trials=self.max_trials, t=self.t, out=cb,
                                   dt_scene=None if sub is None else sub["dt_k"], **self._bp)
         # the accepted pose: the kernel's value, the gradient of p + v dt_used (a zero rotation increment carries no gradient to the geometry)
         self.v = v_new
         if js is not None:                                                 # joint.move(dt): rot1 += body1.v[0] dt (constraints.py:39-43)
             self.Je = js.jacobian(cb.p_out, v=v_new.detach().contiguous(), dt_scene=cb.dt_used)
-        if js is not None and js.pose_dependent:
-            self.p, self._p_geom, self._jrot_ad = _StateUpdate.apply(p_start, p_geo, self._jrot_ad, v_new, cb.p_out, js.jrot1.clone(),
-                                                                     cb.dt_used, 1.0, js)
-            self._jrot_src = self.p
-        else:
-            self.p, self._p_geom = _StateUpdate.apply(p_start, p_geo, None, v_new, cb.p_out, None, cb.dt_used, 1.0, None)
-        self._p_geom_src = self.p
+        self._record_move(p_geo, v_new, cb.p_out, cb.dt_used, 1.0)
         if self.post_stab:
             # world.py:109-121: dp = engine.post_stabilization(world) at the moved pose with the contacts found there and the
             # NEW velocities; dp /= 2; the bodies (and the joints) move by dp dt; contacts are detected again
@@ -937,22 +884,31 @@ class ContactWorld:
                                                    frame2.count, Je2, opts)
             ps = opts["last_post_stab"]
             torch.bitwise_or(self.sticky_status, ps["status"], out=self.sticky_status)
-            p_mid, g_mid = self.p, self._p_geom
             if js is not None:                                             # the joints follow the correction move (world.py:112-116)
                 self.Je = js.jacobian(p_corr, v=dp_s.detach().contiguous(), dt_scene=dt_used, vscale=0.5)
-            if pose_dep:
-                self.p, self._p_geom, self._jrot_ad = _StateUpdate.apply(p_mid, g_mid, self._jrot_ad, dp_s, p_corr, js.jrot1.clone(), dt_used,
-                                                                         0.5, js)
-                self._jrot_src = self.p
-            else:
-                self.p, self._p_geom = _StateUpdate.apply(p_mid, g_mid, None, dp_s, p_corr, None, dt_used, 0.5, None)
-            self._p_geom_src = self.p
+            self._record_move(self._p_geom, dp_s, p_corr, dt_used, 0.5)
             self.contacts = ct.find_contacts(self.geom, p_corr, maxc=self.maxc, eps=self.eps, **self._bp)   # world.py:121
             out = dict(out)
             out["post_stab"] = ps
         ret = dict(out)
         ret["v_new"] = v_new
         return ret
+
+    def _record_move(self, p_geo, v, p_out, dt_used, scale):
+        """The move `p += scale v dt_used` the kernels have made (`p_out`: the pose they accepted) as the `_StateUpdate` node of the
+        graph: the new `p`, the pose the geometry is differentiated at (moved from `p_geo`) and, with pose-dependent joints, the revolute
+        joints' angles (which `JointSet.jacobian` has already moved) - each remembered with the pose tensor it belongs to."""
+        js = self.joints if self.joints is not None and self.joints.pose_dependent else None
+        new = _StateUpdate.apply(self.p, p_geo, None if js is None else self._jrot_ad, v, p_out, None if js is None else js.jrot1.clone(),
+                                 dt_used, scale, js)
+        self.p, self._p_geom = new[0], new[1]
+        self._p_geom_src = self.p
+        if js is not None:
+            self._jrot_ad, self._jrot_src = new[2], self.p
+
+    def _forces(self):
+        """The forces of a step [B,nb,3] float32: the constant `f`, or `force_fn` at the scenes' clocks (forces.py:29-48)."""
+        return self.f if self.force_fn is None else self.force_fn(self.t).to(torch.float32).contiguous()
 
     def step(self, differentiable=False, fixed_dt=False, max_substeps=None):
         """`World.step()` = `step_dt(self.dt)` (`world.py:72-122`) for every scene.
@@ -1001,16 +957,16 @@ class ContactWorld:
 
     def _advance(self, fixed=False):
         """`step_dt` (`world.py:83-122`) for every scene: with dt = `self.dt`, or (`fixed`) with `self._end_t - t` per scene."""
-        if getattr(self, "_autograd_owned", False):
+        if self._autograd_owned:
             # the state tensors are outputs of the autograd graph (their storage belongs to the retired contact buffers of the last
             # differentiable step): the double buffering below must not hand them to a kernel as an output slot
             # - and the contact buffers of the last differentiable step (dt_used, the accepted pose) are saved in that graph
             self.p, self.v, self._autograd_owned = self.p.detach().clone(), self.v.detach().clone(), False
             self.contacts = self.contacts.clone()
-            self._graphs, self._graphs_fixed, self._phase = {}, {}, 0                            # (no graph captured before these buffers existed may replay)
+            self._drop_graphs()                                          # (no graph captured before these buffers existed may replay)
         self._phase ^= 1                                                 # (the parity of the double buffers: one flip per swap below)
         cb = self.contacts
-        f = self.f if self.force_fn is None else self.force_fn(self.t).to(torch.float32).contiguous()
+        f = self._forces()
         count, dt_solve, sub = cb.count, self.dt, None
         if fixed:
             # dt_k = end_t - t per scene (0: finished); the solve forms u = M v + dt_k f as M v + 1 * fl(float(dt_k) f) - the same fp32

@@ -17,6 +17,7 @@ import torch
 
 from .. import _lib
 from ..lcp.lcp import LCPFunction
+from ..scenes import eq_rows
 
 
 def _cross(a, b):
@@ -116,7 +117,7 @@ def _run(kind, phys, lists, count, Je, dt, opts):
     v = phys["v"]
     B, nb, _ = v.shape
     maxc, dev = c_n.shape[1], v.device
-    e = 0 if Je is None or Je.numel() == 0 else Je.shape[1]
+    e = eq_rows(Je)
     f64 = opts.get("compute", "f64") == "f64"
     dd = torch.float64 if f64 else torch.float32
     up = lambda t: None if t is None else t.to(dd)

@@ -20,6 +20,11 @@ DT = 1.0 / 30.0          # physics/utils.py:27-28
 GAP = 0.05               # inside the eps = 0.1 detection margin (physics/utils.py:16)
 
 
+def eq_rows(Je):
+    """The equality rows `e` of a joint Jacobian `Je` [B,e,3nb]: none for None and for an empty tensor."""
+    return 0 if Je is None or Je.numel() == 0 else Je.shape[1]
+
+
 @dataclass
 class SceneBatch:
     """Structure-of-arrays description of B independent 2-D rigid-body scenes.

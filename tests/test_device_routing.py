@@ -168,3 +168,21 @@ def test_forward_tag_and_backward(case, call, tag, bwd):
     got_tag, got_bwd = call()
     print(case, "tag", got_tag, "backward", got_bwd)
     assert (got_tag, got_bwd) == (tag, bwd), case
+
+
+@pytest.mark.gpu
+def test_fused_step_backward_is_solve_dynamics_backward_on_the_same_record():
+    """The two host entries of `lcp_step_backward_je_f32` on ONE forward record: every gradient, Je's included, bit for bit."""
+    from lcp_physics_amd.physics.batched_world import fused_step, fused_step_backward, solve_dynamics_backward
+    sc = _scene("stack")
+    e = sc.Je.shape[1]
+    out = fused_step(sc)
+    dl = torch.randn(B, sc.nb, 3, generator=torch.Generator().manual_seed(1)).to(DEV)
+    ga = fused_step_backward(sc, out, dl, want_Je=True)
+    gb = solve_dynamics_backward(B, sc.nb, sc.nc, e, sc.Mdiag, sc.v, sc.f, sc.rest, sc.fric, _buffers(sc), sc.Je, sc.dt, dl, out,
+                                 want_Je=True)
+    torch.cuda.synchronize()
+    assert e == 3 and sorted(ga) == sorted(gb) == sorted(("Mdiag", "v", "f", "rest", "fric", "c_n", "c_p1", "c_p2", "Je"))
+    for k in ga:
+        assert ga[k].shape == gb[k].shape and _finite({k: ga[k]})
+        assert torch.equal(ga[k].view(torch.int32), gb[k].view(torch.int32)), k

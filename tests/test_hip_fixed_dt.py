@@ -400,12 +400,33 @@ def test_fixed_dt_run_from_a_graph_equals_the_eager_run():
     b, _ = _grad_demo_world(range(8))
     b.run(nsteps, graph=True, fixed_dt=True, max_substeps=8)
     torch.cuda.synchronize()
-    assert b._graphs_fixed and not b._graphs, "nothing was captured"
+    assert b._graphs and all(K == 8 for _, K in b._graphs), "nothing was captured"
     sa, sb = _snapshot(a), _snapshot(b)
     for n in STATE + FRAME:
         assert _bits(sa[n], sb[n]), n
     with pytest.raises(ValueError):
         b.run(2, graph=True, fixed_dt=True)
+    # both modes on ONE world: fixed and plain runs alternate, the odd plain count flips the buffer parity between the two K = 8 runs, and
+    # K = 9 is a second sub-step count on a world that already holds fixed-interval graphs.  Three plain steps are spent on the warm-up
+    # (two) and the tail (one), so a five-step plain run follows to put a plain graph next to the fixed ones; the last run replays the
+    # graph of the FIRST, across everything captured in between.
+    runs = [(4, 8), (3, None), (4, 8), (4, 9), (5, None), (2, 8)]         # (steps, max_substeps; None: plain steps)
+    a, _ = _grad_demo_world(range(8))
+    b, _ = _grad_demo_world(range(8))
+    for r, (n, K) in enumerate(runs):
+        mode = {} if K is None else {"fixed_dt": True, "max_substeps": K}
+        for _ in range(n):
+            a.step(**mode)
+            if K is not None:
+                print("run", r, "K", K, "sub-steps of the eager twin", a.substeps.tolist())
+        b.run(n, graph=True, **mode)
+        torch.cuda.synchronize()
+        sa, sb = _snapshot(a), _snapshot(b)
+        for name in STATE + FRAME:
+            assert _bits(sa[name], sb[name]), (r, name)
+    assert not bool(a.behind.any()) and not bool(b.behind.any())
+    assert {K for _, K in b._graphs} == {None, 8, 9}, "plain and fixed graphs side by side"
+    assert len(b._graphs) == 4 and not a._graphs                          # (parity 0 and 1 at K = 8, one each at K = 9 and for plain steps)
 
 
 def test_fixed_dt_rollout_gradient_matches_the_reference_autograd():
