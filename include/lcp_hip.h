@@ -560,6 +560,49 @@ int lcp_body_properties_backward_f64(int B, int nb, int cap, const int32_t* kind
                                      const float* g_Mdiag, const float* g_f,
                                      double* g_verts_raw, double* g_radius, double* g_mass, void* stream);
 
+/* ---- drawing: frames and segmentation masks of every scene, differentiable ----
+ * What Body.draw paints (physics/bodies.py:140-150 circles, :237-250 hulls: pixel = pos * pixels_per_meter, x to the right, y
+ * downward, thickness 0 = filled, > 0 = an outline) in the order of the paint loop of run_world (world.py:279-280: list order,
+ * later over earlier), for B scenes in one launch (lcp_render.hip) - what Recorder (utils.py:54-72) and
+ * run_world(screen=, recorder=) (world.py:246-320) need of the world state, as tensors.  Not drawn: the circle's spoke, the
+ * hull's centre dot, the joints' markers, a hull of fewer than three vertices.
+ *   camera: H x W pixels, pixel (i, j) sampled at x = (x0 + (j + 1/2) / ppm, y0 + (i + 1/2) / ppm); w > 0: the width of the edge
+ *       ramp in world units (one pixel: 1 / ppm).
+ *   signed distance d_k(x): circle |x - c| - r; hull with w_i = c + R(rot) v_i (utils.py:105-112), e_i = w_i+1 - w_i,
+ *       n_i = left_orthogonal(e_i) / |e_i| (contacts.py:229-231), h_i = n_i . (x - w_i), m = max h_i: d = m where m <= 0, else
+ *       the distance to the nearest edge segment.  cov(d) = clamp(1/2 - d / w, 0, 1); alpha_k = cov(d_k) for thickness_k == 0,
+ *       cov(d_k) - cov(d_k + thickness_k) for thickness_k > 0.
+ *   in: kind[B,nb] i32, radius[B,nb] f64, verts_local[B,nb,nvcap,2] f64 (slots >= nverts are never read), nverts[B,nb] i32,
+ *       p[B,nb,3] f64 (rot, x, y), colors[B,nb,C] f32, background[C] f32 - all required; thickness[B,nb] f64, NULL = all filled.
+ *   out (each optional, at least one; written, never accumulated):
+ *       image[B,C,H,W] f32: I = background, then I = I (1 - alpha_k) + alpha_k colors[b,k] for k = 0 .. nb-1;
+ *       ids[B,H,W] i32: the largest k with d_k <= 0 (the filled silhouette, whatever the thickness), or -1.
+ * Sizes: 1 <= nb <= 64, 8 <= nvcap <= 64, 0 <= scene_verts_max <= 1024 (as lcp_move_find_contacts_nv_f64; a scene with more hull
+ * vertices than scene_verts_max is not drawn: background and -1), B, H, W >= 1, 1 <= C <= 4, B C H W < 2^31, w > 0, ppm > 0 -
+ * anything else is LCP_E_BADARG before any launch.  fp64 arithmetic.  One workgroup per (scene, tile of 16 x 64 pixels); a body
+ * whose bounding circle grown by w / 2 misses the tile is skipped, where its alpha is exactly 0.  No allocation, no
+ * synchronisation, no global state. */
+int lcp_render_f64(int B, int nb, int nvcap, int scene_verts_max, int H, int W, int C,
+                   const int32_t* kind, const double* radius, const double* verts_local, const int32_t* nverts,
+                   const double* p, const float* colors, const float* background, const double* thickness,
+                   double x0, double y0, double ppm, double w,
+                   float* image, int32_t* ids, void* stream);
+
+/* Backward of the image of lcp_render_f64: what autograd gives the pose, Circle.rad, Hull.verts and the colours when the
+ * drawing of Body.draw (bodies.py:140-150, 237-250) in the order of world.py:279-280 is written as tensor operations.  Same
+ * inputs and checks; nothing is saved by the forward, the compositing state is recomputed per pixel.
+ *   in: g_image[B,C,H,W] f32 (required).
+ *   out (each optional, at least one; written, never accumulated): g_p[B,nb,3] f64, g_radius[B,nb] f64 (hulls: 0),
+ *       g_verts_local[B,nb,nvcap,2] f64 (body frame; circles and slots >= nverts: 0), g_colors[B,nb,C] f32.
+ * cov differentiates to -1 / w strictly inside its ramp and to 0 elsewhere; at |x - c| = 0 the circle's direction is 0.
+ * One workgroup per (scene, body) over the body's pixel box, clamped to the image in floating point; sums in a fixed order, no
+ * atomics: two runs give the same bits. */
+int lcp_render_backward_f64(int B, int nb, int nvcap, int scene_verts_max, int H, int W, int C,
+                            const int32_t* kind, const double* radius, const double* verts_local, const int32_t* nverts,
+                            const double* p, const float* colors, const float* background, const double* thickness,
+                            double x0, double y0, double ppm, double w, const float* g_image,
+                            double* g_p, double* g_radius, double* g_verts_local, float* g_colors, void* stream);
+
 /* ---- debugging / A-B aids (not part of the drop-in surface) ----
  * lcp_debug_set_trace: when non-NULL, the dense forward writes trace[B, max_iter, 4] =
  *   (resid, mu, sigma, alpha) per PDIPM iteration (device pointer to doubles).

@@ -728,4 +728,38 @@ int lcp_body_properties_backward_f64(int B, int nb, int cap, const int32_t* kind
                                               g_inertia, g_Mdiag, g_f, g_verts_raw, g_radius, g_mass, stream);
 }
 
+// what both render entries refuse before any launch: sizes outside the packed vertex list's, a camera without pixels or scale, an
+// image whose element index leaves 31 bits, a missing required pointer (thickness is optional: NULL = every body filled)
+static bool render_args_ok(int B, int nb, int nvcap, int scene_verts_max, int H, int W, int C, const void* kind, const void* radius,
+                           const void* verts_local, const void* nverts, const void* p, const void* colors, const void* background,
+                           double ppm, double w) {
+  if (B < 1 || !lcp::render_supported(nb, nvcap, scene_verts_max)) return false;
+  if (C < 1 || C > 4 || H < 1 || W < 1) return false;
+  if ((long long)B * C * H * W >= (1LL << 31)) return false;
+  if (!(w > 0.0) || !(ppm > 0.0)) return false;                      // (a NaN fails both)
+  return kind && radius && verts_local && nverts && p && colors && background;
+}
+
+int lcp_render_f64(int B, int nb, int nvcap, int scene_verts_max, int H, int W, int C, const int32_t* kind, const double* radius,
+                   const double* verts_local, const int32_t* nverts, const double* p, const float* colors, const float* background,
+                   const double* thickness, double x0, double y0, double ppm, double w, float* image, int32_t* ids, void* stream) {
+  if (!render_args_ok(B, nb, nvcap, scene_verts_max, H, W, C, kind, radius, verts_local, nverts, p, colors, background, ppm, w))
+    return LCP_E_BADARG;
+  if (!image && !ids) return LCP_E_BADARG;                            // (nothing asked for)
+  return lcp::render_launch(B, nb, nvcap, scene_verts_max, H, W, C, kind, radius, verts_local, nverts, p, colors, background, thickness,
+                            x0, y0, ppm, w, image, ids, stream);
+}
+
+int lcp_render_backward_f64(int B, int nb, int nvcap, int scene_verts_max, int H, int W, int C, const int32_t* kind,
+                            const double* radius, const double* verts_local, const int32_t* nverts, const double* p,
+                            const float* colors, const float* background, const double* thickness, double x0, double y0, double ppm,
+                            double w, const float* g_image, double* g_p, double* g_radius, double* g_verts_local, float* g_colors,
+                            void* stream) {
+  if (!render_args_ok(B, nb, nvcap, scene_verts_max, H, W, C, kind, radius, verts_local, nverts, p, colors, background, ppm, w))
+    return LCP_E_BADARG;
+  if (!g_image || (!g_p && !g_radius && !g_verts_local && !g_colors)) return LCP_E_BADARG;
+  return lcp::render_backward_launch(B, nb, nvcap, scene_verts_max, H, W, C, kind, radius, verts_local, nverts, p, colors, background,
+                                     thickness, x0, y0, ppm, w, g_image, g_p, g_radius, g_verts_local, g_colors, stream);
+}
+
 }  // extern "C"

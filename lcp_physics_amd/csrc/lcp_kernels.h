@@ -258,6 +258,17 @@ int body_properties_backward_launch(int B, int nb, int cap, const int32_t* kind,
                                     const double* g_verts_local, const double* g_inertia, const float* g_Mdiag, const float* g_f,
                                     double* g_verts_raw, double* g_radius, double* g_mass, void* stream);
 
+// lcp_render.hip: frames and masks of every scene (Body.draw, bodies.py:140-150, 237-250; world.py:279-280) and their backward
+bool render_supported(int nb, int nvcap, int scene_verts_max);          // the sizes of the packed vertex list (contacts_wide_supported)
+int render_launch(int B, int nb, int nvcap, int scene_verts_max, int H, int W, int C, const int32_t* kind, const double* radius,
+                  const double* verts_local, const int32_t* nverts, const double* p, const float* colors, const float* background,
+                  const double* thickness, double x0, double y0, double ppm, double w, float* image, int32_t* ids, void* stream);
+int render_backward_launch(int B, int nb, int nvcap, int scene_verts_max, int H, int W, int C, const int32_t* kind,
+                           const double* radius, const double* verts_local, const int32_t* nverts, const double* p,
+                           const float* colors, const float* background, const double* thickness, double x0, double y0, double ppm,
+                           double w, const float* g_image, double* g_p, double* g_radius, double* g_verts_local, float* g_colors,
+                           void* stream);
+
 // backward of the contact frame with respect to the SHAPE (radii, body-frame hull vertices) at the same sizes: one lane per
 // (contacting pair, shape coordinate the pair's records were built from) - lcp_contacts_shape.hip
 int contact_frame_backward_shape_launch(int B, int nb, int maxc, int nvcap, int scene_verts_max, const int32_t* kind,

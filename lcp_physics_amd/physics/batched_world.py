@@ -1011,3 +1011,9 @@ class ContactWorld:
 
     def get_p(self):
         return self.p
+
+    def render(self, cam, colors, **kw):
+        """The current frame of every scene, `image [B,C,H,W]` float32 (`physics.render.render(self.geom, self.p, cam, colors, **kw)`:
+        Body.draw in the paint order of world.py:279-280).  After `step(differentiable=True)` the image is part of the roll-out's graph."""
+        from .render import render
+        return render(self.geom, self.p, cam, colors, **kw)
