@@ -14,33 +14,20 @@
 //   * the triangular sweeps run in wave 0 (two pivots per lane, the solution entries broadcast by v_readlane, no barrier per step);
 //     the pinned coordinates' rows give dy_p = rhs_p - (S dx)_p afterwards;
 //   * reductions over the scene: per wave by DPP, the four partial results combined in a fixed order through LDS.
+// Sizes, reductions, LU, sweeps and the products with the A image are lcp_primal_wg_common.h, shared with lcp_primal_wg_poststab.hip.
 // PDIPM semantics are lcp_primal_kernel's (pdipm.py:49-179): init shift, best iterate, NaN never improving, `lim` strikes, 0.999,
 // step lengths through reciprocals with the exact cold path of lcp_device.h; the backward re-forms the system at the kept iterate
 // with the floored D and one step of iterative refinement on the unreduced equations (lcp_primal_step.inc).
-#include "lcp_primal_common.h"
+#include "lcp_primal_wg_common.h"
 
 namespace lcp {
 namespace pwg {
 
-using namespace w64;
-using namespace wsc;
+using namespace wgc;
 
-constexpr int NT = 256;                 // threads per scene
-constexpr int CAP = 128;                // pivots
 constexpr int RCAP = CAP + 1;           // rows of the image (pinned form: the three pinned coordinates' rows + at most 126 pivots)
-// row stride: entry (r, c) in bank pair (r LDK + c) mod 32 - LDK = 1 (mod 32) spreads the diagonal blocks of the bodies over the banks
-// (formation) and puts the entries of one column in different banks (the sweeps read a column across the lanes)
-constexpr int LDK = CAP + 1;
-constexpr int AST = 132;                // row stride of the A image (nz <= 129)
-constexpr int MAXC = 256;               // contacts
 // workspace per scene (doubles): [0] contact count | x [IT, IT + 136) | y [YO, YO + 8) | z, s: 4 ncap each, component-major
-constexpr int IT = 8, YO = IT + 136, ZO = YO + 8;
-__host__ __device__ constexpr size_t ws_doubles(int ncap) { return (size_t)ZO + 8 * (size_t)ncap; }
-
-__device__ __forceinline__ void bsync() { __syncthreads(); }
-__device__ __forceinline__ void lds_add_wg(double* p, double v) {
-  __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);     // ds_add_f64 (no return)
-}
+__host__ __device__ constexpr size_t ws_doubles(int ncap) { return wgc::ws_doubles(ncap, 8); }
 
 template <bool BWD>
 __global__ void __launch_bounds__(NT, 1) lcp_primal_wg_kernel(StepArgs SP, StepBwdArgs Gd, int pin) {
@@ -60,28 +47,12 @@ __global__ void __launch_bounds__(NT, 1) lcp_primal_wg_kernel(StepArgs SP, StepB
   double* const Wg = (double*)SP.ws + (size_t)scene * ws_doubles(ncap);
 
   // ---- scene-wide reductions: per wave by DPP, then the four wave results in a fixed order ------------------------------------
-  auto bsum = [&](double v) LCP_INL -> double {
-    const double w = wave_sum(v);
-    bsync(); if (lane == 0) redd[wv] = w; bsync();
-    return (redd[0] + redd[1]) + (redd[2] + redd[3]);
-  };
-  auto bmin = [&](double v) LCP_INL -> double {                                   // NaN-ignoring, as wave_min
-    const double w = wave_min(v);
-    bsync(); if (lane == 0) redd[wv] = w; bsync();
-    return __builtin_fmin(__builtin_fmin(redd[0], redd[1]), __builtin_fmin(redd[2], redd[3]));
-  };
-  auto bumax = [&](uint32_t v) LCP_INL -> uint32_t {
-    const uint32_t w = wave_umax(v);
-    bsync(); if (lane == 0) redu[wv] = w; bsync();
-    return umax(umax(redu[0], redu[1]), umax(redu[2], redu[3]));
-  };
-  auto bor = [&](uint32_t v) LCP_INL -> uint32_t {                                // OR of a five-bit word
-    const uint32_t w = (__any((v & 1u) != 0u) ? 1u : 0u) | (__any((v & 2u) != 0u) ? 2u : 0u) | (__any((v & 4u) != 0u) ? 4u : 0u) |
-                       (__any((v & 8u) != 0u) ? 8u : 0u) | (__any((v & 16u) != 0u) ? 16u : 0u);
-    bsync(); if (lane == 0) redu[wv] = w; bsync();
-    return (redu[0] | redu[1]) | (redu[2] | redu[3]);
-  };
-  auto bany = [&](bool b) LCP_INL -> bool { return bumax(b ? 1u : 0u) != 0u; };
+  const BlockReduce br{redd, redu, wv, lane};
+  auto bsum = [&](double v) LCP_INL -> double { return br.sum(v); };
+  auto bmin = [&](double v) LCP_INL -> double { return br.min(v); };
+  auto bumax = [&](uint32_t v) LCP_INL -> uint32_t { return br.umax(v); };
+  auto bor = [&](uint32_t v) LCP_INL -> uint32_t { return br.or_<5>(v); };          // OR of a five-bit word
+  auto bany = [&](bool b) LCP_INL -> bool { return br.any(b); };
 
   const int lx = tid < nz ? tid : 0;
   const float md_l = ((const float*)SP.Mdiag)[(size_t)scene * nz + lx], vv_l = ((const float*)SP.v)[(size_t)scene * nz + lx];
@@ -160,20 +131,8 @@ __global__ void __launch_bounds__(NT, 1) lcp_primal_wg_kernel(StepArgs SP, StepB
     bsync();
     return r;
   };
-  auto Av = [&](double v) LCP_INL -> double {                                     // equality threads <- x threads (unpinned form)
-    xv[tid] = vx ? v : 0.0; bsync();
-    double out = 0;
-    if (ve) { const float* ar = At + ya * AST; for (int k = 0; k < nz; ++k) out = fma((double)ar[k], xv[k], out); }
-    bsync();
-    return out;
-  };
-  auto Aty = [&](double y) LCP_INL -> double {                                    // x threads <- equality threads (unpinned form)
-    xv[tid] = ve ? y : 0.0; bsync();
-    double acc = 0;
-    if (vx) for (int a = 0; a < e; ++a) acc = fma((double)At[a * AST + tid], xv[nz + a], acc);
-    bsync();
-    return acc;
-  };
+  auto Av = [&](double v) LCP_INL -> double { return wgc::Av(At, xv, v, tid, nz, vx, ve, ya); };        // equality threads <- x threads (unpinned form)
+  auto Aty = [&](double y) LCP_INL -> double { return wgc::Aty(At, xv, y, tid, nz, e, vx, ve); };      // x threads <- equality threads (unpinned form)
 
   // ---- the contact's 4 x 4 block M = F_c + diag(s / z), inverted in closed form (lcp_primal_step.inc) ------------------------
   double idn = 1, i1 = 1, i2 = 1, kap = 1.0 / 3.0, b00 = 0, b10 = 0, b11 = 0;
@@ -219,70 +178,13 @@ __global__ void __launch_bounds__(NT, 1) lcp_primal_wg_kernel(StepArgs SP, StepB
       }
       bsync();
     }
-    // right-looking LU, one barrier per pivot: the pivot row in registers, wave w takes the rows k + 1 + w + 4 i
-    bool bad = false;
-    for (int k = 0; k < n; ++k) {
-      const double* prow = Kl + (k + clo) * LDK;
-      const double piv = prow[k];
-      bad = bad || !(piv != 0.0) || (piv != piv);
-      const double inv = fast_rcp(piv);
-      const int j0 = k + 1 + lane, j1 = j0 + 64;
-      const double u0 = j0 < n ? prow[j0] : 0.0, u1 = j1 < n ? prow[j1] : 0.0;
-      for (int i = k + 1 + wv; i < n; i += 4) {
-        double* row = Kl + (i + clo) * LDK;
-        const double l = row[k] * inv;
-        if (j0 < n) row[j0] = fma(-l, u0, row[j0]);
-        if (j1 < n) row[j1] = fma(-l, u1, row[j1]);
-        if (lane == 0) row[k] = l;                                        // (after every lane's read of it: LDS serves a wave in order)
-      }
-      bsync();
-    }
-    singular = bad;                                                       // (uniform: every thread read every pivot)
+    singular = lu_factor(Kl, n, clo, wv, lane);                           // right-looking LU, one barrier per pivot
   };
   // K^-1 w (w: entry `tid` of the right-hand side, coordinate layout; the solution comes back the same way)
   auto ksolve = [&](double w) LCP_INL -> double {
     rv[tid] = w;
     bsync();
-    if (wv == 0) {
-      const int i0 = lane, i1 = lane + 64;
-      const bool l0 = i0 < n, l1 = i1 < n;
-      const double* r0p = Kl + ((l0 ? i0 : 0) + clo) * LDK;
-      const double* r1p = Kl + ((l1 ? i1 : 0) + clo) * LDK;
-      double r0 = l0 ? rv[i0 + clo] : 0.0, r1 = l1 ? rv[i1 + clo] : 0.0;
-      // forward: unit lower factor, eight columns' entries asked for ahead of their steps
-      for (int k0 = 0; k0 < n; k0 += 8) {
-        double a0[8], a1[8];
-#pragma unroll
-        for (int kk = 0; kk < 8; ++kk) { const int k = k0 + kk < n ? k0 + kk : n - 1; a0[kk] = r0p[k]; a1[kk] = r1p[k]; }
-#pragma unroll
-        for (int kk = 0; kk < 8; ++kk) {
-          const int k = k0 + kk;
-          if (k < n) {
-            const double yk = bcast_lane(k < 64 ? r0 : r1, k & 63);
-            if (l0 && i0 > k) r0 = fma(-a0[kk], yk, r0);
-            if (l1 && i1 > k) r1 = fma(-a1[kk], yk, r1);
-          }
-        }
-      }
-      const double ud0 = l0 ? fast_rcp(r0p[i0]) : 1.0, ud1 = l1 ? fast_rcp(r1p[i1]) : 1.0;
-      // backward: upper factor, x_k = r_k / U[k][k]
-      for (int k0 = n - 1; k0 >= 0; k0 -= 8) {
-        double a0[8], a1[8];
-#pragma unroll
-        for (int kk = 0; kk < 8; ++kk) { const int k = k0 - kk >= 0 ? k0 - kk : 0; a0[kk] = r0p[k]; a1[kk] = r1p[k]; }
-#pragma unroll
-        for (int kk = 0; kk < 8; ++kk) {
-          const int k = k0 - kk;
-          if (k >= 0) {
-            const double xk = bcast_lane(k < 64 ? r0 * ud0 : r1 * ud1, k & 63);
-            if (l0 && i0 < k) r0 = fma(-a0[kk], xk, r0);
-            if (l1 && i1 < k) r1 = fma(-a1[kk], xk, r1);
-          }
-        }
-      }
-      if (l0) rv[i0 + clo] = r0 * ud0;
-      if (l1) rv[i1 + clo] = r1 * ud1;
-    }
+    if (wv == 0) lu_sweeps(Kl, rv, n, clo, lane);
     bsync();
     double out = rv[tid];
     if (pin && tid < clo) {                                               // dy_p = rhs_p - (S dx)_p on the pinned coordinates' rows
@@ -574,16 +476,15 @@ __global__ void __launch_bounds__(NT, 1) lcp_primal_wg_kernel(StepArgs SP, StepB
 
 // sizes: at most 128 pivots (pinned form: nz - 3; otherwise nz + neq with neq <= 4), at most 256 contacts
 bool primal_wg_supported(int nz, int m, int e, bool pinned) {
-  if (nz <= 0 || (nz % 3) != 0 || (m % 4) != 0 || m / 4 > pwg::MAXC || e < 0) return false;
-  if (pinned && e == 3) return nz - e <= pwg::CAP && nz <= pwg::RCAP;
-  return e <= 4 && nz + e <= pwg::CAP;
+  if (pinned && e == 3) return wgc::sizes_ok(nz, m, e) && nz - e <= wgc::CAP && nz <= pwg::RCAP;
+  return wgc::general_form_fits(nz, m, e);
 }
 size_t primal_wg_ws_bytes(int m) { return sizeof(double) * pwg::ws_doubles(m / 4); }
 
 template <bool BWD>
 static int wg_launch(const StepArgs& SP, const StepBwdArgs& Gd, bool pinned, void* stream) {
   const int pin = (pinned && SP.e == 3) ? 1 : 0;
-  hipLaunchKernelGGL(pwg::lcp_primal_wg_kernel<BWD>, dim3(SP.B), dim3(pwg::NT), 0, (hipStream_t)stream, SP, Gd, pin);
+  hipLaunchKernelGGL(pwg::lcp_primal_wg_kernel<BWD>, dim3(SP.B), dim3(wgc::NT), 0, (hipStream_t)stream, SP, Gd, pin);
   return hipGetLastError() == hipSuccess ? 0 : LCP_E_LAUNCH;
 }
 int primal_wg_step(const StepArgs& SP, void* stream, bool pinned) { StepBwdArgs Gd = {}; return wg_launch<false>(SP, Gd, pinned, stream); }

@@ -7,28 +7,17 @@
 // Thread c = contact c, thread r < nz + neq = entry r of x / y.  Formation by ds_add_f64 wave by wave (a barrier between the
 // passes: every entry receives its additions in one order on every launch and at every batch position), right-looking LU without
 // pivoting with one barrier per pivot, the triangular sweeps in wave 0, scene-wide reductions per wave by DPP and combined in a
-// fixed order.  This unit carries its own copies of those pieces (lcp_primal_wg.hip stays as it was compiled: DESIGN section 6).
-#include "lcp_primal_common.h"
+// fixed order.  Those pieces - sizes, reductions, LU, sweeps, the products with the A image - are lcp_primal_wg_common.h, shared
+// with lcp_primal_wg.hip.
+#include "lcp_primal_wg_common.h"
 
 namespace lcp {
 namespace pwp {
 
-using namespace w64;
-using namespace wsc;
+using namespace wgc;
 
-constexpr int NT = 256;                 // threads per scene
-constexpr int CAP = 128;                // pivots
-constexpr int LDK = CAP + 1;            // row stride of the image (lcp_primal_wg.hip: 1 mod 32)
-constexpr int AST = 132;                // row stride of the A image
-constexpr int MAXC = 256;               // contacts
 // workspace per scene (doubles): [0] contact count | x [IT, IT + 136) | y [YO, YO + 8) | z [ncap] | s [ncap]
-constexpr int IT = 8, YO = IT + 136, ZO = YO + 8;
-__host__ __device__ constexpr size_t ws_doubles(int ncap) { return (size_t)ZO + 2 * (size_t)ncap; }
-
-__device__ __forceinline__ void bsync() { __syncthreads(); }
-__device__ __forceinline__ void lds_add_wg(double* p, double v) {
-  __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);     // ds_add_f64 (no return)
-}
+__host__ __device__ constexpr size_t ws_doubles(int ncap) { return wgc::ws_doubles(ncap, 2); }
 
 template <bool BWD>
 __global__ void __launch_bounds__(NT, 1) lcp_poststab_wg_kernel(StepArgs SP, StepBwdArgs Gd) {
@@ -47,32 +36,13 @@ __global__ void __launch_bounds__(NT, 1) lcp_poststab_wg_kernel(StepArgs SP, Ste
   double* const Wg = (double*)SP.ws + (size_t)scene * ws_doubles(ncap);
 
   // ---- scene-wide reductions: per wave by DPP, then the four wave results in a fixed order ------------------------------------
-  auto bsum = [&](double v) LCP_INL -> double {
-    const double w = wave_sum(v);
-    bsync(); if (lane == 0) redd[wv] = w; bsync();
-    return (redd[0] + redd[1]) + (redd[2] + redd[3]);
-  };
-  auto bmin = [&](double v) LCP_INL -> double {                                   // NaN-ignoring, as wave_min
-    const double w = wave_min(v);
-    bsync(); if (lane == 0) redd[wv] = w; bsync();
-    return __builtin_fmin(__builtin_fmin(redd[0], redd[1]), __builtin_fmin(redd[2], redd[3]));
-  };
-  auto bmax = [&](double v) LCP_INL -> double {                                   // NaN-ignoring, as wave_max
-    const double w = wave_max(v);
-    bsync(); if (lane == 0) redd[wv] = w; bsync();
-    return __builtin_fmax(__builtin_fmax(redd[0], redd[1]), __builtin_fmax(redd[2], redd[3]));
-  };
-  auto bumax = [&](uint32_t v) LCP_INL -> uint32_t {
-    const uint32_t w = wave_umax(v);
-    bsync(); if (lane == 0) redu[wv] = w; bsync();
-    return umax(umax(redu[0], redu[1]), umax(redu[2], redu[3]));
-  };
-  auto bor = [&](uint32_t v) LCP_INL -> uint32_t {                                // OR of a three-bit word
-    const uint32_t w = (__any((v & 1u) != 0u) ? 1u : 0u) | (__any((v & 2u) != 0u) ? 2u : 0u) | (__any((v & 4u) != 0u) ? 4u : 0u);
-    bsync(); if (lane == 0) redu[wv] = w; bsync();
-    return (redu[0] | redu[1]) | (redu[2] | redu[3]);
-  };
-  auto bany = [&](bool b) LCP_INL -> bool { return bumax(b ? 1u : 0u) != 0u; };
+  const BlockReduce br{redd, redu, wv, lane};
+  auto bsum = [&](double v) LCP_INL -> double { return br.sum(v); };
+  auto bmin = [&](double v) LCP_INL -> double { return br.min(v); };
+  auto bmax = [&](double v) LCP_INL -> double { return br.max(v); };
+  auto bumax = [&](uint32_t v) LCP_INL -> uint32_t { return br.umax(v); };
+  auto bor = [&](uint32_t v) LCP_INL -> uint32_t { return br.or_<3>(v); };          // OR of a three-bit word
+  auto bany = [&](bool b) LCP_INL -> bool { return br.any(b); };
 
   const int lx = tid < nz ? tid : 0;
   const float md_l = ((const float*)SP.Mdiag)[(size_t)scene * nz + lx], vv_l = ((const float*)SP.v)[(size_t)scene * nz + lx];
@@ -136,20 +106,8 @@ __global__ void __launch_bounds__(NT, 1) lcp_poststab_wg_kernel(StepArgs SP, Ste
     bsync();
     return r;
   };
-  auto Av = [&](double v) LCP_INL -> double {                                     // equality threads <- x threads
-    xv[tid] = vx ? v : 0.0; bsync();
-    double out = 0;
-    if (ve) { const float* ar = At + ya * AST; for (int k = 0; k < nz; ++k) out = fma((double)ar[k], xv[k], out); }
-    bsync();
-    return out;
-  };
-  auto Aty = [&](double y) LCP_INL -> double {                                    // x threads <- equality threads
-    xv[tid] = ve ? y : 0.0; bsync();
-    double acc = 0;
-    if (vx) for (int a = 0; a < e; ++a) acc = fma((double)At[a * AST + tid], xv[nz + a], acc);
-    bsync();
-    return acc;
-  };
+  auto Av = [&](double v) LCP_INL -> double { return wgc::Av(At, xv, v, tid, nz, vx, ve, ya); };        // equality threads <- x threads
+  auto Aty = [&](double y) LCP_INL -> double { return wgc::Aty(At, xv, y, tid, nz, e, vx, ve); };      // x threads <- equality threads
   const double b_in = (e > 0) ? Av((double)vv_l) : 0.0;                   // ge = Je v (engines.py:86), on the equality threads
 
   // ---- formation + LU of K = [[M + Jc^T diag(z / s) Jc, A^T], [A, 0]] ---------------------------------------------------------
@@ -175,70 +133,13 @@ __global__ void __launch_bounds__(NT, 1) lcp_poststab_wg_kernel(StepArgs SP, Ste
       }
       bsync();
     }
-    // right-looking LU, one barrier per pivot: the pivot row in registers, wave w takes the rows k + 1 + w + 4 i
-    bool bad = false;
-    for (int k = 0; k < n; ++k) {
-      const double* prow = Kl + k * LDK;
-      const double piv = prow[k];
-      bad = bad || !(piv != 0.0) || (piv != piv);
-      const double inv = fast_rcp(piv);
-      const int j0 = k + 1 + lane, j1 = j0 + 64;
-      const double u0 = j0 < n ? prow[j0] : 0.0, u1 = j1 < n ? prow[j1] : 0.0;
-      for (int i = k + 1 + wv; i < n; i += 4) {
-        double* row = Kl + i * LDK;
-        const double l = row[k] * inv;
-        if (j0 < n) row[j0] = fma(-l, u0, row[j0]);
-        if (j1 < n) row[j1] = fma(-l, u1, row[j1]);
-        if (lane == 0) row[k] = l;                                        // (after every lane's read of it: LDS serves a wave in order)
-      }
-      bsync();
-    }
-    singular = bad;                                                       // (uniform: every thread read every pivot)
+    singular = lu_factor(Kl, n, 0, wv, lane);                             // right-looking LU, one barrier per pivot
   };
   // K^-1 w (w: entry `tid` of the right-hand side; the solution comes back the same way)
   auto ksolve = [&](double w) LCP_INL -> double {
     rv[tid] = w;
     bsync();
-    if (wv == 0) {
-      const int i0 = lane, i1 = lane + 64;
-      const bool l0 = i0 < n, l1 = i1 < n;
-      const double* r0p = Kl + (l0 ? i0 : 0) * LDK;
-      const double* r1p = Kl + (l1 ? i1 : 0) * LDK;
-      double r0 = l0 ? rv[i0] : 0.0, r1 = l1 ? rv[i1] : 0.0;
-      // forward: unit lower factor, eight columns' entries asked for ahead of their steps
-      for (int k0 = 0; k0 < n; k0 += 8) {
-        double a0[8], a1[8];
-#pragma unroll
-        for (int kk = 0; kk < 8; ++kk) { const int k = k0 + kk < n ? k0 + kk : n - 1; a0[kk] = r0p[k]; a1[kk] = r1p[k]; }
-#pragma unroll
-        for (int kk = 0; kk < 8; ++kk) {
-          const int k = k0 + kk;
-          if (k < n) {
-            const double yk = bcast_lane(k < 64 ? r0 : r1, k & 63);
-            if (l0 && i0 > k) r0 = fma(-a0[kk], yk, r0);
-            if (l1 && i1 > k) r1 = fma(-a1[kk], yk, r1);
-          }
-        }
-      }
-      const double ud0 = l0 ? fast_rcp(r0p[i0]) : 1.0, ud1 = l1 ? fast_rcp(r1p[i1]) : 1.0;
-      // backward: upper factor, x_k = r_k / U[k][k]
-      for (int k0 = n - 1; k0 >= 0; k0 -= 8) {
-        double a0[8], a1[8];
-#pragma unroll
-        for (int kk = 0; kk < 8; ++kk) { const int k = k0 - kk >= 0 ? k0 - kk : 0; a0[kk] = r0p[k]; a1[kk] = r1p[k]; }
-#pragma unroll
-        for (int kk = 0; kk < 8; ++kk) {
-          const int k = k0 - kk;
-          if (k >= 0) {
-            const double xk = bcast_lane(k < 64 ? r0 * ud0 : r1 * ud1, k & 63);
-            if (l0 && i0 < k) r0 = fma(-a0[kk], xk, r0);
-            if (l1 && i1 < k) r1 = fma(-a1[kk], xk, r1);
-          }
-        }
-      }
-      if (l0) rv[i0] = r0 * ud0;
-      if (l1) rv[i1] = r1 * ud1;
-    }
+    if (wv == 0) lu_sweeps(Kl, rv, n, 0, lane);
     bsync();
     const double out = rv[tid];
     bsync();
@@ -472,14 +373,13 @@ __global__ void __launch_bounds__(NT, 1) lcp_poststab_wg_kernel(StepArgs SP, Ste
 
 // sizes: the general form of lcp_primal_wg.hip - at most 128 pivots (nz + neq, neq <= 4), at most 256 contacts
 bool primal_wg_poststab_supported(int nz, int m, int e) {
-  if (nz <= 0 || (nz % 3) != 0 || m <= 0 || (m % 4) != 0 || m / 4 > pwp::MAXC || e < 0) return false;
-  return e <= 4 && nz + e <= pwp::CAP;
+  return m > 0 && wgc::general_form_fits(nz, m, e);
 }
 size_t primal_wg_poststab_ws_bytes(int m) { return sizeof(double) * pwp::ws_doubles(m / 4); }
 
 template <bool BWD>
 static int wg_poststab_launch(const StepArgs& SP, const StepBwdArgs& Gd, void* stream) {
-  hipLaunchKernelGGL(pwp::lcp_poststab_wg_kernel<BWD>, dim3(SP.B), dim3(pwp::NT), 0, (hipStream_t)stream, SP, Gd);
+  hipLaunchKernelGGL(pwp::lcp_poststab_wg_kernel<BWD>, dim3(SP.B), dim3(wgc::NT), 0, (hipStream_t)stream, SP, Gd);
   return hipGetLastError() == hipSuccess ? 0 : LCP_E_LAUNCH;
 }
 int primal_wg_post_stab(const StepArgs& SP, void* stream) { StepBwdArgs Gd = {}; return wg_poststab_launch<false>(SP, Gd, stream); }
