@@ -603,6 +603,54 @@ int lcp_render_backward_f64(int B, int nb, int nvcap, int scene_verts_max, int H
                             double x0, double y0, double ppm, double w, const float* g_image,
                             double* g_p, double* g_radius, double* g_verts_local, float* g_colors, void* stream);
 
+/* ---- the breakout encoder: frames -> paddle, blocks and ball of every scene ----
+ * What extract_params (experiments/breakout/encoder.py:63-133, with remove_rect :136-137 and get_pos_dims :140-145) reads off
+ * an Atari Breakout frame, for B frames in one launch (lcp_encoder.hip).  The reference reads channel 0 only (`frame[..., 0]`):
+ * the KEY PLANE k(i, j) = frame[b stride_b + i stride_row + j stride_col], bytes, every comparison on bytes.  "Removed" stands
+ * for what the reference paints black (remove_rect) before it searches on.
+ *   layout: a HOST pointer to LCP_ENC_LAYOUT_WORDS int32 words, copied into the kernel's arguments (defaults: encoder.py:28-52):
+ *       [0] paddle_line 189  [1] paddle_h 4  [2] paddle_w 16  [3] paddle_key 200  [4] ball_w 2  [5] nrows 6 (0 .. 8)
+ *       [6] band_top 57  [7] band_h 6  [8..15] row_key 200 198 180 162 72 66  [16..19] erase rect, inclusive corners (top, left,
+ *       bottom, right) 189 152 194 160  [20] ball_key 200
+ *   paddle (:67-82): px = the first column holding the maximum of row paddle_line; if k(paddle_line, px + ball_w + 1) !=
+ *       paddle_key, the first column >= px + ball_w + 1 holding the maximum of the rest of the row (the ball can sit in that row,
+ *       left of the paddle); r = the first column >= px that is not paddle_key (none, or r == px: W), at most px + paddle_w.
+ *       Corners (paddle_line, px, paddle_line + paddle_h, r); removed: rows paddle_line .. paddle_line + paddle_h, columns
+ *       px .. r, both inclusive, clipped.  px + ball_w + 1 >= W (the reference raises): the first px is kept,
+ *       LCP_ENC_ST_PADDLE_PROBE.
+ *   blocks (:91-101): band i has top = band_top + i band_h; the maximal runs [left, right) of k(top, .) == row_key[i], left to
+ *       right, give corners (top, left, top + band_h, right) and remove rows top .. top + band_h - 1, columns left .. right - 1.
+ *       A run that starts at column 0 ends the band's list: it and what follows it there are neither listed nor removed
+ *       (`while left > 0`).  A run that reaches column W - 1 (the reference never returns) ends the band's list the same way:
+ *       LCP_ENC_ST_RUN_AT_EDGE.  Order: by band, then left to right.  nblocks is the true total; the first max_blocks are
+ *       stored, more set LCP_ENC_ST_TRUNCATED; the removal covers every listed run whatever max_blocks.
+ *   erase rect (:104-105): removed, inclusive, clipped.
+ *   ball (:107-121): (i, j) = the first pixel in raster order with k == ball_key that is not removed; right = the first column
+ *       >= j of row i that is removed or not ball_key (none: j), bottom likewise down column j (none: i).  Corners (i, j, bottom,
+ *       right).  No such pixel: LCP_ENC_ST_NO_BALL and zeros.
+ *   in: frame (device) with stride_b, stride_row, stride_col > 0 in bytes (gym's [B,H,W,C]: stride_col = C; [B,C,H,W]: 1).  Of
+ *       each row only the bytes from its first to its last key byte are read, nothing before or after; rows with stride_col <= 4
+ *       are read as whole 16-byte lines (any alignment), other strides byte by byte.
+ *   out (each optional, NULL = skipped, at least one; written, never accumulated): paddle[B,4] i32, blocks[B,max_blocks,4] i32
+ *       (slots >= the count: 0), nblocks[B] i32, ball[B,4] i32, status[B] i32 (LCP_ENC_ST_*), and the get_pos_dims form
+ *       (x, y, w, h) = ((right + left) / 2, (bottom + top) / 2, right - left, bottom - top) in f64: paddle_params[B,4],
+ *       block_params[B,max_blocks,4] (slots >= the count: the reference's placeholder (1000, 60, 1, 1), run_breakout.py:56),
+ *       ball_params[B,3] = (x, y, min(min(w, h) / 2, 1)), without a ball (W / 2, 100 H, 1) (:125-129).
+ * LCP_E_BADARG before any launch: a NULL frame or layout, no output, B < 0, H outside 1 .. 2^20, W outside 1 .. 1024, max_blocks
+ * outside 1 .. 256, a stride < 1, a key outside 1 .. 255, nrows outside 0 .. 8, band_h < 1, paddle_w < 1, paddle_h < 0, ball_w < 0,
+ * paddle_line or band_top outside the image, band_top + nrows band_h > paddle_line, an erase rect with a negative or reversed
+ * corner.  B == 0: success, no launch.  One workgroup of 256 threads per scene; no allocation, no synchronisation, no global
+ * state, no atomics on global memory: two runs give the same bits. */
+#define LCP_ENC_LAYOUT_WORDS 21
+#define LCP_ENC_ST_NO_BALL       1  /* no pixel of ball_key is left once paddle, blocks and the erase rect are removed           */
+#define LCP_ENC_ST_TRUNCATED     2  /* nblocks > max_blocks: the list is cut, nothing else                                         */
+#define LCP_ENC_ST_RUN_AT_EDGE   4  /* a band's run reaches column W - 1: the reference loops forever (encoder.py:96-101)          */
+#define LCP_ENC_ST_PADDLE_PROBE  8  /* px + ball_w + 1 >= W: the reference raises IndexError (encoder.py:69)                       */
+int lcp_extract_params_u8(int B, int H, int W, const uint8_t* frame, int64_t stride_b, int64_t stride_row, int64_t stride_col,
+                          const int32_t* layout, int max_blocks,
+                          int32_t* paddle, int32_t* blocks, int32_t* nblocks, int32_t* ball, int32_t* status,
+                          double* paddle_params, double* block_params, double* ball_params, void* stream);
+
 /* ---- debugging / A-B aids (not part of the drop-in surface) ----
  * lcp_debug_set_trace: when non-NULL, the dense forward writes trace[B, max_iter, 4] =
  *   (resid, mu, sigma, alpha) per PDIPM iteration (device pointer to doubles).

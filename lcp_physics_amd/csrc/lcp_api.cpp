@@ -762,4 +762,31 @@ int lcp_render_backward_f64(int B, int nb, int nvcap, int scene_verts_max, int H
                                      thickness, x0, y0, ppm, w, g_image, g_p, g_radius, g_verts_local, g_colors, stream);
 }
 
+// the layout words of lcp_extract_params_u8 against an H x W image (include/lcp_hip.h lists what is refused)
+static bool encoder_layout_ok(const int32_t* w, int H, int W) {
+  const int paddle_line = w[0], paddle_h = w[1], paddle_w = w[2], paddle_key = w[3], ball_w = w[4], nrows = w[5], band_top = w[6],
+            band_h = w[7], ball_key = w[20];
+  auto key = [](int k) { return k >= 1 && k <= 255; };
+  if (!key(paddle_key) || !key(ball_key) || nrows < 0 || nrows > 8) return false;
+  for (int i = 0; i < nrows; ++i)
+    if (!key(w[8 + i])) return false;
+  if (band_h < 1 || paddle_w < 1 || paddle_h < 0 || ball_w < 0) return false;
+  if (paddle_line < 0 || paddle_line >= H || band_top < 0 || band_top >= H) return false;
+  if ((long long)band_top + (long long)nrows * band_h > paddle_line) return false;          // (every top line lies above it)
+  if (paddle_h > (1 << 20) || paddle_w > (1 << 20) || ball_w > (1 << 20)) return false;      // (sums with a column stay in 31 bits)
+  return w[16] >= 0 && w[17] >= 0 && w[18] >= w[16] && w[19] >= w[17];
+}
+
+int lcp_extract_params_u8(int B, int H, int W, const uint8_t* frame, int64_t stride_b, int64_t stride_row, int64_t stride_col,
+                          const int32_t* layout, int max_blocks, int32_t* paddle, int32_t* blocks, int32_t* nblocks, int32_t* ball,
+                          int32_t* status, double* paddle_params, double* block_params, double* ball_params, void* stream) {
+  if (B < 0 || H < 1 || H > (1 << 20) || W < 1 || W > 1024 || max_blocks < 1 || max_blocks > 256) return LCP_E_BADARG;
+  if (!frame || !layout || stride_b < 1 || stride_row < 1 || stride_col < 1) return LCP_E_BADARG;
+  if (!paddle && !blocks && !nblocks && !ball && !status && !paddle_params && !block_params && !ball_params) return LCP_E_BADARG;
+  if (!encoder_layout_ok(layout, H, W)) return LCP_E_BADARG;
+  if (B == 0) return 0;
+  return lcp::extract_params_launch(B, H, W, frame, stride_b, stride_row, stride_col, layout, max_blocks, paddle, blocks, nblocks, ball,
+                                    status, paddle_params, block_params, ball_params, stream);
+}
+
 }  // extern "C"

@@ -269,6 +269,12 @@ int render_backward_launch(int B, int nb, int nvcap, int scene_verts_max, int H,
                            double w, const float* g_image, double* g_p, double* g_radius, double* g_verts_local, float* g_colors,
                            void* stream);
 
+// lcp_encoder.hip: the breakout encoder (experiments/breakout/encoder.py:63-145), one workgroup per frame; arguments checked by
+// the caller, `layout` the LCP_ENC_LAYOUT_WORDS host words
+int extract_params_launch(int B, int H, int W, const uint8_t* frame, long long stride_b, long long stride_row, long long stride_col,
+                          const int32_t* layout, int max_blocks, int32_t* paddle, int32_t* blocks, int32_t* nblocks, int32_t* ball,
+                          int32_t* status, double* paddle_params, double* block_params, double* ball_params, void* stream);
+
 // backward of the contact frame with respect to the SHAPE (radii, body-frame hull vertices) at the same sizes: one lane per
 // (contacting pair, shape coordinate the pair's records were built from) - lcp_contacts_shape.hip
 int contact_frame_backward_shape_launch(int B, int nb, int maxc, int nvcap, int scene_verts_max, const int32_t* kind,
