@@ -36,6 +36,12 @@
 #ifndef LCP_Q_ROWL
 #define LCP_Q_ROWL 0          // 1: the pinned body-space kernel reads its contact's rows of Jc / Jt from LDS instead of keeping them in registers
 #endif
+#ifndef LCP_Q_FORM_BLOCKS
+#define LCP_Q_FORM_BLOCKS 1   // size-specialised pinned forward with register columns: K = Q + G^T M^-1 G formed per (group of four contacts, body block of three columns) and only where the wave's Jacobian rows are not all exact zeros there (SceneQ::block_masks; 0: the dense formation, A/B)
+#endif
+#ifndef LCP_Q_FORM_BLOCKS_BWD
+#define LCP_Q_FORM_BLOCKS_BWD 0   // the same in bwd_solve_body (one formation per launch, the weights of a group read from LDS when its first block is met).  Measured and OFF: dense backward 23.75 / 23.84 us without, 23.89 / 23.91 us with it (profiles/r11_ab_form_blocks.txt) - the kernel is bound by its stores
+#endif
 #ifndef LCP_Q_BEST_LDS
 #define LCP_Q_BEST_LDS 1      // 0: the pinned body-space kernel keeps its best iterate in registers (A/B aid)
 #endif
@@ -106,6 +112,12 @@ template <int C0> __device__ __forceinline__ void gtw8_dpp(double& a0, double& a
 #define LCP_Q_ASM_PRODUCTS 1
 #endif
 
+// LCP_Q_FORM_BLOCKS: where the block form of the formation applies - rows in registers (the masks are read from them), the free columns
+// CLO .. CHI-1 in whole body blocks, and the caller WANTS it (register columns in the forward, LCP_Q_FORM_BLOCKS_BWD in the backward).
+// The one condition both the call of SceneQ::block_masks and factor_pq's choice are made from.
+template <bool WANT, int CLO, int CHI> __host__ __device__ constexpr bool form_blocks_apply() {
+  return WANT && (LCP_Q_FORM_BLOCKS != 0) && (LCP_Q_ROWL == 0) && CHI > CLO && (CHI - CLO) % 3 == 0 && (CHI - CLO) / 3 <= 4;
+}
 // ---------------------------------------------------------------- per-lane scene data and products
 // An x-space vector: entry 16 h + l16 of the scene's nz-vector for h < XH (XH = 1: nz <= 16, the tuned headline case;
 // XH = 2: nz <= 32, six to ten bodies).
@@ -122,6 +134,22 @@ struct SceneQ {
     if constexpr (COLR) static_for<16>([&](auto C) LCP_INL { gcol[C] = (TC)L.GL[C * RS + l16]; tcol[C] = (TC)L.GTL[C * RS + l16]; });
   }
   static constexpr int RS = 16 * XH;     // row length of GL / GTL / AtL
+  static constexpr bool COLR_ = COLR;
+  // LCP_Q_FORM_BLOCKS: bit 4 g + b of `fmask` (wave-uniform) is set when any of the contacts 4g .. 4g+3 of any of the wave's four scenes has
+  // an entry other than an exact zero (a NaN counts as present) in the columns CLO + 3b .. CLO + 3b + 2 of its rows of Jc / Jt.  Taken from
+  // the rows themselves, whichever loader filled them; padded and dead contact lanes hold zero rows and set nothing.  Once per kernel.
+  mutable unsigned fmask = 0xffffu;      // (all ones until block_masks() has run: every block formed)
+  template <int CLO, int NB> __device__ __forceinline__ void block_masks() const {
+    static_assert(!ROWL && XH == 1 && NB <= 4, "rows in registers, one bit per (group, block)");
+    unsigned m = 0;
+    static_for<NB>([&](auto B_) LCP_INL {
+      constexpr int J = CLO + 3 * B_;
+      const bool any = !(jc[J] == (TI)0) || !(jc[J + 1] == (TI)0) || !(jc[J + 2] == (TI)0) || !(jt[J] == (TI)0) || !(jt[J + 1] == (TI)0) || !(jt[J + 2] == (TI)0);
+      const unsigned long long bal = __ballot(any);
+      static_for<4>([&](auto G_) LCP_INL { if (bal & (0x000F000F000F000FULL << (4 * G_))) m |= 1u << (4 * G_ + B_); });
+    });
+    fmask = m;
+  }
   LdsQ<TI, TC> L;
   int nz, nc, e, l16;      // nc: live contacts of THIS scene (row-uniform)
   int ncw, ncap;          // ncw: max nc over the scenes of the wave (loop bound); ncap: contact capacity (array strides)
@@ -480,7 +508,8 @@ __device__ __forceinline__ M4<TC> minv_pq(const PQ& R, const SQ& S, const M4<TC>
   o.f2 = R.i2 * (t.f2 - o.g);
   return o;
 }
-template <typename TI, typename TC, typename PQ, typename SQ>
+// FB_LDS: the caller has run S.block_masks() although the scene keeps no register columns (see LCP_Q_FORM_BLOCKS below)
+template <typename TI, typename TC, typename PQ, bool FB_LDS = false, typename SQ>
 __device__ __forceinline__ bool factor_pq(TC (&xr)[20], TC (&er)[20], PQ& R, const SQ& S, const M4<TC>& D,
                                           bool valid LCP_QPROF_ARG) {
   const int l16 = launder(S.l16), ncw = PQ::NCF_ > 0 ? PQ::NCF_ : __builtin_amdgcn_readfirstlane(S.ncw);
@@ -512,6 +541,16 @@ __device__ __forceinline__ bool factor_pq(TC (&xr)[20], TC (&er)[20], PQ& R, con
       });
     }
   }
+  // LCP_Q_FORM_BLOCKS (register columns, free columns in whole body blocks): per group of four contacts and body block one scalar test of
+  // the wave's mask and one statement of 24 multiply-adds.  A block that is left out would have added a x (+-0) to accumulators that are
+  // +0 or Q's diagonal or sums of such terms - never -0 - so every xr[J] is bit for bit what the dense formation below leaves, as long as
+  // the weights b00 / b10 / b11 are finite (a NaN weight no longer reaches the columns where the contact's rows are zero: such a scene
+  // carries LCP_ST_NAN either way).  The masks subsume the `ncw` guards: dead contact lanes have zero rows.
+  // (A wave whose mask is nearly full pays more than the dense form - a statement keeps only three accumulators busy: an interleaved contact
+  //  list, all 16 bits, runs the forward in 51.3 instead of 48.6 us.  Sending such waves to a second, dense copy of the formation was
+  //  measured and dropped: the copy in the loop cost the stack its whole gain - profiles/r11_ab_form_blocks.txt.)
+  constexpr bool FBLK = PQ::TRIM_ && form_blocks_apply<SQ::COLR_ || FB_LDS, CLO, CHI>() && std::is_same<TC, double>::value;
+  auto form_dense = [&]() LCP_INL
   {
     const TI* gl = S.L.GL + l16 + oz;
     const TI* gtl = S.L.GTL + l16 + oz;
@@ -538,7 +577,27 @@ __device__ __forceinline__ bool factor_pq(TC (&xr)[20], TC (&er)[20], PQ& R, con
         });
       }
     });
-  }
+  };
+  if constexpr (FBLK) {
+    const unsigned fm = S.fmask;
+    static_for<4>([&](auto G_) LCP_INL {
+      constexpr int C0 = 4 * G_;
+      if constexpr (SQ::COLR_) {
+        const TC a4[4] = {S.gcol[C0], S.gcol[C0 + 1], S.gcol[C0 + 2], S.gcol[C0 + 3]}, b4[4] = {S.tcol[C0], S.tcol[C0 + 1], S.tcol[C0 + 2], S.tcol[C0 + 3]};
+        static_for<(CHI - CLO) / 3>([&](auto B_) LCP_INL {
+          if (fm & (1u << (C0 + B_))) pq_form_block<C0, CLO + 3 * B_>(xr, p0, p1, a4, b4);
+        });
+      } else if (fm & (0xfu << C0)) {                        // (weights of matrix row l16 from LDS, once per group that has a block)
+        const TI* gl = S.L.GL + l16 + oz;
+        const TI* gtl = S.L.GTL + l16 + oz;
+        TC a4[4], b4[4];
+        static_for<4>([&](auto I) LCP_INL { a4[I] = (TC)gl[(C0 + I) * 16]; b4[I] = (TC)gtl[(C0 + I) * 16]; });
+        static_for<(CHI - CLO) / 3>([&](auto B_) LCP_INL {
+          if (fm & (1u << (C0 + B_))) pq_form_block<C0, CLO + 3 * B_>(xr, p0, p1, a4, b4);
+        });
+      }
+    });
+  } else form_dense();
   LCP_QTICK(pr, 1)                                                               // formation
   bool singular = false;
   R.udx = 1; R.ude = 1;
@@ -1096,6 +1155,7 @@ __global__ void __launch_bounds__(64, (ALG == 2 ? LCP_Q_OCC2 : 1)) lcp_fwd_quad(
     // do the equality rows pin the first neq coordinates (A = [I 0], b = 0) in all four scenes of the wave ?  (or are there none)
     __syncthreads();                                                     // (the A rows the loaders put into LDS)
     S.load_columns();
+    if constexpr (form_blocks_apply<COLR, EF, NZF>()) S.template block_masks<EF, (NZF - EF) / 3>();
 #ifdef LCP_Q_PROFILE
     __builtin_amdgcn_s_waitcnt(0);
     pr_t2 = clock64();
@@ -1510,7 +1570,9 @@ __device__ __forceinline__ void bwd_solve_body(const SceneQ<TI, TC, 1>& S, bool 
     R.pin_rt = PINB ? true : (__all(okl) != 0);
   }
   TC xr[20], er[20];
-  factor_pq<TI, TC, PQb>(xr, er, R, S, dfl, vc LCP_QPROF_PASS);                               // lcp.py:46
+  constexpr bool FBB = PQb::TRIM_ && form_blocks_apply<(LCP_Q_FORM_BLOCKS_BWD != 0), EF, NZF>();
+  if constexpr (FBB) S.template block_masks<EF, (NZF - EF) / 3>();
+  factor_pq<TI, TC, PQb, FBB>(xr, er, R, S, dfl, vc LCP_QPROF_PASS);                          // lcp.py:46
   const M4<TC> zero = m4<TC>(0, 0, 0, 0);
   XV<TC, 1> rx, ox;
 #if LCP_Q_BWD_ONE_SOLVE

@@ -435,6 +435,19 @@ template <int J0> struct GvN<J0, 8> { static __device__ __forceinline__ void run
 template <int K, int J0, int N> __device__ __forceinline__ void pq_formN(double (&xr)[20], const double (&p0)[16], const double (&p1)[16], double a, double b) {
   if constexpr (N > 0) PqFormN<K, J0, N>::run(xr, p0, p1, a, b);
 }
+// formation by (contact group, body block) - LCP_Q_FORM_BLOCKS: the four contacts C0 .. C0+3 (weights a[0..3], b[0..3]) over the three columns
+// J0 .. J0+2 in ONE statement (24 instructions behind one `s_nop 1`; 17 register operands).  Every column receives its terms in the order of the per-contact
+// forms above - contacts ascending, the p0 term before the p1 term - so a caller that runs the statements of a column with C0 ascending and
+// leaves out only those whose p0 / p1 are all +-0 gets the accumulators of the dense formation bit for bit.
+#define LCP_PQB_ONE(X, P, M, K) "v_fmac_f64_dpp %[" #X "], %[" #P "], %[" #M "] row_newbcast:%[" #K "] " LCP_DPP_FULL "\n\t"
+#define LCP_PQB_CONTACT(A, B, K) LCP_PQB_ONE(x0, p0, A, K) LCP_PQB_ONE(x1, p1, A, K) LCP_PQB_ONE(x2, p2, A, K) LCP_PQB_ONE(x0, q0, B, K) LCP_PQB_ONE(x1, q1, B, K) LCP_PQB_ONE(x2, q2, B, K)
+template <int C0, int J0> __device__ __forceinline__ void pq_form_block(double (&xr)[20], const double (&p0)[16], const double (&p1)[16], const double (&a)[4], const double (&b)[4]) {
+  asm("s_nop 1\n\t" LCP_PQB_CONTACT(a0, b0, k0) LCP_PQB_CONTACT(a1, b1, k1) LCP_PQB_CONTACT(a2, b2, k2) LCP_PQB_CONTACT(a3, b3, k3)
+      : [x0] "+v"(xr[J0 + 0]), [x1] "+v"(xr[J0 + 1]), [x2] "+v"(xr[J0 + 2])
+      : [p0] "v"(p0[J0 + 0]), [q0] "v"(p1[J0 + 0]), [p1] "v"(p0[J0 + 1]), [q1] "v"(p1[J0 + 1]), [p2] "v"(p0[J0 + 2]), [q2] "v"(p1[J0 + 2]),
+        [a0] "v"(a[0]), [b0] "v"(b[0]), [a1] "v"(a[1]), [b1] "v"(b[1]), [a2] "v"(a[2]), [b2] "v"(b[2]), [a3] "v"(a[3]), [b3] "v"(b[3]),
+        [k0] "n"(C0 + 0), [k1] "n"(C0 + 1), [k2] "n"(C0 + 2), [k3] "n"(C0 + 3));
+}
 template <int J0, int N> __device__ __forceinline__ void gvN_dpp(double& n0, double& n1, double& t0, double& t1, double v, const double (&c)[8], const double (&t)[8]) {
   if constexpr (N > 0) GvN<J0, N>::run(n0, n1, t0, t1, v, c, t);
 }

@@ -43,7 +43,10 @@ def flops_forward_executed_body_space(nz, nc, e, it, pinned=True, trimmed=None):
     on the floor) factors the nz - e free rows only, otherwise the (nz + e)-square system.  Per KKT solve: one J^T w and one J v,
     the two triangular sweeps and the closed-form 4 x 4 block inverses (~60 per contact).  `trimmed` (the size-specialised
     instantiations: compile-time nz / neq, pinned): only the columns e .. nz-1 are formed and multiplied - nz rows x (nz - e)
-    columns per contact in the formation, nz - e terms in J v.  Nothing of the contact-space pre-factorisation is formed."""
+    columns per contact in the formation, nz - e terms in J v.  Nothing of the contact-space pre-factorisation is formed.
+    NOTE (LCP_Q_FORM_BLOCKS): the size-specialised pinned kernels with register columns no longer execute the dense formation counted
+    here - they form only the (group of four contacts, body block) pairs that are not all zeros in the wave, 7 of 16 on the stack - so
+    `bench.py`'s `frac`, which uses this count, overstates their executed FLOPs; `frac_necessary` is the closer figure."""
     if trimmed is None:
         trimmed = pinned and (nz, e) in SIZED_SHAPES
     n = (nz - e) if pinned else (nz + e)
