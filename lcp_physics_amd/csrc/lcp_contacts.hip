@@ -23,7 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "lcp_kernels.h"
+#include "lcp_contacts_wide.h"
 
 namespace lcp {
 namespace ct {
@@ -39,23 +39,7 @@ constexpr int MAXB = 32;       // max bodies per scene handled by the detection 
 // (the reference builds the contact tuple with differentiable torch operations, contacts.py:57-352; its autograd follows the
 //  branches the forward pass took - so does this: every comparison looks at the values only)
 namespace ad {
-struct Dual {
-  double v, d;
-  __device__ __forceinline__ Dual() {}
-  __device__ __forceinline__ Dual(double a) : v(a), d(0.0) {}
-  __device__ __forceinline__ Dual(double a, double b) : v(a), d(b) {}
-};
-__device__ __forceinline__ Dual operator+(Dual a, Dual b) { return Dual(a.v + b.v, a.d + b.d); }
-__device__ __forceinline__ Dual operator-(Dual a, Dual b) { return Dual(a.v - b.v, a.d - b.d); }
-__device__ __forceinline__ Dual operator-(Dual a) { return Dual(-a.v, -a.d); }
-__device__ __forceinline__ Dual operator*(Dual a, Dual b) { return Dual(a.v * b.v, a.d * b.v + a.v * b.d); }
-__device__ __forceinline__ Dual operator/(Dual a, Dual b) { const double q = a.v / b.v; return Dual(q, (a.d - q * b.d) / b.v); }
-__device__ __forceinline__ Dual sqrt(Dual a) { const double r = ::sqrt(a.v); return Dual(r, 0.5 * a.d / r); }
-__device__ __forceinline__ bool operator<(Dual a, Dual b) { return a.v < b.v; }
-__device__ __forceinline__ bool operator<=(Dual a, Dual b) { return a.v <= b.v; }
-__device__ __forceinline__ bool operator>(Dual a, Dual b) { return a.v > b.v; }
-__device__ __forceinline__ bool operator>=(Dual a, Dual b) { return a.v >= b.v; }
-__device__ __forceinline__ bool operator==(Dual a, Dual b) { return a.v == b.v; }
+using ctw::ad::Dual;             // (lcp_contacts_wide.h; its operators are found through their arguments)
 #define LCP_S Dual
 #include "lcp_contacts_geom.inc"
 #undef LCP_S
@@ -70,6 +54,9 @@ __device__ __forceinline__ bool operator==(Dual a, Dual b) { return a.v == b.v; 
 // trial (identical stores) until its neighbours are done.
 // DTS: the loop of every scene starts from P.dt_in[scene] (World.step(fixed_dt=True), world.py:72-80); a compile-time choice, so that the
 // scalar-dt instantiations are the code they were (with a run-time test they measured 3 % slower on the 4-box world: profiles/r10_fixed_dt.json).
+// The pair decode, the record store, the penetration reduction, the accept-or-halve rule, the padding and the per-scene outputs are those of
+// lcp_contacts_wide.h in this kernel's own text, for the same reason: with any one of those helpers in place the instruction stream of every
+// instantiation changes (profiles/contacts_shared_staging.json).  An edit to either text belongs in both.
 template <int LPS, int NBMAX, bool DTS>
 __global__ void __launch_bounds__(64) lcp_move_find_contacts_kernel(ContactArgs P) {
   constexpr int SPW = 64 / LPS;                                 // scenes per wave
@@ -232,6 +219,7 @@ __global__ void __launch_bounds__(FB_T) lcp_contact_frame_backward_kernel(int B,
                                                                         const int32_t* count, const float* g_n, const float* g_p1,
                                                                         const float* g_p2, double* dp) {
   using V2 = ad::V2; using Body = ad::Body; using Pt = ad::Pt; using Dual = ad::Dual;      // (functions: found through their arguments)
+  using ad::v2;                                                                            // (but for the one whose arguments are all Dual)
   // the pair's rotated vertices, edge normals and edge lengths (dual numbers, indexed by run-time vertex numbers): per-thread
   // slices of LDS - as local arrays they were 1296 B of scratch memory per lane.  (+1 element per slice: the threads' slices start
   // on different banks)

@@ -11,7 +11,7 @@
 // A pair's records depend on few shape coordinates: the two radii, the two vertices of the reference edge (hull / hull; for
 // circle / hull the GJK simplex's one or two vertices, or the SAT edge's two) and the two vertices of the incident edge - ten seeds
 // at most, whatever the hulls' vertex counts.  One workgroup per scene:
-//   1. the work units = the distinct pairs among the first min(count, maxc) records (as in the pose kernel);
+//   1. the work units = the distinct pairs among the first min(count, maxc) records (stage_frame_scene, as in the pose kernel);
 //   2. one lane per unit runs collide_pair with no seed and keeps the vertices LCP_GEOM_TRACE names (on dual numbers too, so
 //      that this pass and the next take their branches in the same code);
 //   3. one lane per (unit, seed) re-runs collide_pair with that seed and keeps its term g . d(n, p1, p2) in LDS;
@@ -130,64 +130,14 @@ __global__ void __launch_bounds__(SB_T) lcp_contact_frame_backward_shape_kernel(
   const int scene = blockIdx.x;
   double* out_r = d_radius ? d_radius + (size_t)scene * nb : nullptr;
   double* out_v = d_verts_local ? d_verts_local + (size_t)scene * nb * nvcap * 2 : nullptr;
-  int ntot = count[scene];
-  ntot = ntot < 0 ? 0 : (ntot > maxc ? maxc : ntot);
   const int vtot = stage_bodies(scene, nb, nvcap, kind, nverts, radius, s_kind, s_off, s_rad);   // (uniform over the workgroup)
   if (vtot > vmax) {                                                      // scene_verts_max too small: no derivative
     if (out_r) for (int i = tid; i < nb; i += SB_T) out_r[i] = 0.0;
     if (out_v) for (int i = tid; i < nb * nvcap * 2; i += SB_T) out_v[i] = 0.0;
     return;
   }
-  for (int i = tid; i < nb * 3; i += SB_T) s_pose[i] = p[(size_t)scene * nb * 3 + i];
-  // the work units: wave 0 flags the records that start a pair and compacts their indices with a ballot
-  if (tid < 64) {
-    int nu = 0;
-    for (int r0 = 0; r0 < ntot; r0 += 64) {
-      const int r = r0 + tid;
-      int i1 = 0, i2 = 0;
-      bool start = false;
-      if (r < ntot) {
-        const size_t o = (size_t)scene * maxc + r;
-        i1 = c_i1[o]; i2 = c_i2[o];
-        start = r == 0 || i1 != c_i1[o - 1] || i2 != c_i2[o - 1];
-        i1 = i1 < 0 ? 0 : (i1 >= nb ? nb - 1 : i1); i2 = i2 < 0 ? 0 : (i2 >= nb ? nb - 1 : i2);   // (body indices stay in the table)
-      }
-      const uint64_t m = __ballot(start);
-      if (start) {
-        const int u = nu + __popcll(m & ((1ull << tid) - 1));
-        s_ustart[u] = r; s_ub1[u] = i1; s_ub2[u] = i2;
-      }
-      nu += __popcll(m);
-    }
-    if (tid == 0) { s_ustart[nu] = ntot; s_nunits = nu; }
-  }
-  __syncthreads();
-  for (int b = tid; b < nb; b += SB_T) { const double rot = s_pose[b * 3]; s_sc[b] = make_double2(sin(rot), cos(rot)); }
-  __syncthreads();
-  // rotated vertices, edge normals and lengths (the detection kernel's arithmetic: the same values, hence the same branches)
-  for (int b = 0; b < nb; ++b) {
-    const int o = s_off[b], n = s_off[b + 1] - o;
-    const double* vl = verts_local + ((size_t)scene * nb + b) * nvcap * 2;
-    const double sn = s_sc[b].x, cs = s_sc[b].y;
-    for (int k = tid; k < n; k += SB_T) {
-      const double lx = vl[2 * k], ly = vl[2 * k + 1];
-      s_verts[o + k] = make_double2(cs * lx - sn * ly, sn * lx + cs * ly);          // utils.py:105-112
-    }
-  }
-  __syncthreads();
-  for (int b = 0; b < nb; ++b) {
-    const int o = s_off[b], n = s_off[b + 1] - o;
-    for (int k = tid; k < n; k += SB_T) {
-      const double2 a = s_verts[o + k], c = s_verts[o + (k + 1) % n];
-      const double ex = c.x - a.x, ey = c.y - a.y;
-      const double en = ::sqrt(ex * ex + ey * ey);
-      const double inv = 1.0 / en;
-      s_elen[o + k] = en;
-      s_nrm[o + k] = make_double2(ey * inv, -ex * inv);                             // left_orth(edge) / |edge|
-    }
-  }
-  __syncthreads();
-  const int nunits = s_nunits;
+  const int nunits = stage_frame_scene<SB_T>(scene, nb, maxc, nvcap, verts_local, p, count, c_i1, c_i2, s_off, s_pose, s_sc, s_verts, s_nrm,
+                                             s_elen, s_ustart, s_ub1, s_ub2, &s_nunits);
   // the vertices each unit's records were built from
   for (int u = tid; u < nunits; u += SB_T) {
     const int bi = s_ub1[u], bj = s_ub2[u];

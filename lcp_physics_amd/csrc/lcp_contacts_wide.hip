@@ -12,10 +12,13 @@
 //     edge lengths do not depend on the pose).
 // Limits (checked on the host before a launch, lcp_api.cpp): nb <= 64, 8 <= nvcap <= 64 (verts_local[B,nb,nvcap,2]),
 // hulls of 3..nvcap vertices, at most 1024 vertices per scene.
+// The detection kernel is also the one behind lcp_move_find_contacts_bp_f64: instantiated with BP it culls the body pairs before the
+// narrow phase (lcp_contacts_bp.hip, included below: the cull, its LDS and why it loses nothing).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "lcp_contacts_wide.h"
+#include "lcp_contacts_bp.hip"
 
 namespace lcp {
 namespace ctw {
@@ -59,8 +62,11 @@ struct ConstRef {
 // compacted in pair order with a wave prefix sum.  Dynamic LDS: 4 arrays over the scene's packed vertex list (V = the host's
 // scene_verts_max): local and rotated vertices, edge normals (V2) and edge lengths, and the owning body of each vertex.
 // DTS: every scene's loop starts from P.dt_in[scene] (compile-time, as in lcp_contacts.hip: the scalar-dt kernel stays the code it was)
-template <bool DTS>
-__global__ void __launch_bounds__(64) lcp_move_find_contacts_wide_kernel(ContactArgs P, int nvcap, int vmax) {
+// BP: the broadphase of lcp_contacts_bp.hip - every trial pose culls the pairs into a candidate list (static LDS of its own, which the
+// other instantiations do not allocate) and the lanes walk that list instead of all pairs; candidates[B] or NULL: its length at the
+// accepted pose.  Every barrier and the __all(done) exit are wave-uniform in every instantiation.
+template <bool DTS, bool BP>
+__global__ void __launch_bounds__(64) lcp_move_find_contacts_wide_kernel(ContactArgs P, int nvcap, int vmax, int32_t* candidates) {
   extern __shared__ double2 s_dyn[];
   V2* s_vloc = reinterpret_cast<V2*>(s_dyn);
   V2* s_verts = s_vloc + vmax;
@@ -71,19 +77,15 @@ __global__ void __launch_bounds__(64) lcp_move_find_contacts_wide_kernel(Contact
   __shared__ V2 s_sc[MAXB];
   __shared__ double s_rad[MAXB];
   __shared__ int s_kind[MAXB], s_off[MAXB + 1];
+  __shared__ bp::CullLds<V2> s_cull;                       // (BP only)
   const int ll = threadIdx.x;
   const int scene = blockIdx.x;
   const int nb = P.nb;
   const int npairs = nb * (nb - 1) / 2;
   const int vtot = stage_bodies(scene, nb, nvcap, P.kind, P.nverts, P.radius, s_kind, s_off, s_rad);
   if (vtot > vmax) {                                      // the caller's scene_verts_max is too small: no detection, count = -1
-    for (int slot = ll; slot < P.maxc; slot += 64) {
-      const size_t o = (size_t)scene * P.maxc + slot;
-      P.c_n[o * 2] = 0; P.c_n[o * 2 + 1] = 0; P.c_p1[o * 2] = 0; P.c_p1[o * 2 + 1] = 0; P.c_p2[o * 2] = 0; P.c_p2[o * 2 + 1] = 0;
-      if (P.c_pen) P.c_pen[o] = 0;
-      P.c_i1[o] = 0; P.c_i2[o] = 0;
-    }
-    if (ll == 0) P.count[scene] = -1;
+    pad_records(P, scene, ll, 0);
+    if (ll == 0) { P.count[scene] = -1; if (BP && candidates) candidates[scene] = 0; }
     return;
   }
   __syncthreads();
@@ -93,11 +95,14 @@ __global__ void __launch_bounds__(64) lcp_move_find_contacts_wide_kernel(Contact
     const double* vl = P.verts_local + ((size_t)scene * nb + b) * nvcap * 2;
     for (int k = ll; k < n; k += 64) { s_vloc[o + k] = v2(vl[2 * k], vl[2 * k + 1]); s_vbody[o + k] = b; }
   }
+  if constexpr (BP) {
+    __syncthreads();
+    bp::bound_radii(nb, s_kind, s_off, s_rad, s_vloc, s_cull.bound);
+  }
   double dt = DTS ? P.dt_in[scene] : P.dt;                  // per-scene starting dt (World.step(fixed_dt=True), world.py:72-80)
   const bool finished = DTS && dt <= 0.0;                      // the scene has reached its end_t: it stays where it is (one trial, no move)
-  int base = 0, trial = 0;
+  int base = 0, trial = 0, nwork = npairs;                  // nwork: the pairs the narrow phase walks
   double maxpen = -1e300;
-  bool done = false;
   for (;;) {
     // bodies.py:80-82 (p <- p_start + v dt) and the vertex rotation of bodies.py:211-214
     for (int idx = ll; idx < nb * 3; idx += 64) {
@@ -108,93 +113,55 @@ __global__ void __launch_bounds__(64) lcp_move_find_contacts_wide_kernel(Contact
     __syncthreads();
     for (int b = ll; b < nb; b += 64) { const double rot = s_pose[b * 3]; s_sc[b] = v2(sin(rot), cos(rot)); }
     __syncthreads();
-    for (int idx = ll; idx < vtot; idx += 64) {
-      const int bdy = s_vbody[idx];
-      const double sn = s_sc[bdy].x, cs = s_sc[bdy].y;
-      const double lx = s_vloc[idx].x, ly = s_vloc[idx].y;
-      s_verts[idx] = v2(cs * lx - sn * ly, sn * lx + cs * ly);                      // utils.py:105-112
-    }
+    for (int idx = ll; idx < vtot; idx += 64) s_verts[idx] = turned<V2>(s_sc[s_vbody[idx]], s_vloc[idx].x, s_vloc[idx].y);
     __syncthreads();
     // edge normals and lengths of every hull, once per trial pose
     for (int idx = ll; idx < vtot; idx += 64) {
-      const int bdy = s_vbody[idx], o = s_off[bdy], nvb = s_off[bdy + 1] - o, k = idx - o;
-      const V2 edge = s_verts[o + (k + 1) % nvb] - s_verts[idx];
-      const double en = norm(edge);
-      s_elen[idx] = en;
-      s_nrm[idx] = left_orth(edge) * (1.0 / en);
+      const int bdy = s_vbody[idx], o = s_off[bdy];
+      edge_normal(s_verts + o, s_off[bdy + 1] - o, idx - o, s_nrm[idx], s_elen[idx]);
     }
     __syncthreads();
+    if constexpr (BP) {
+      nwork = bp::cull_pairs(P, scene, s_cull, s_kind, s_off, s_rad, s_pose, s_verts, s_nrm);
+      __syncthreads();
+    }
     base = 0; maxpen = -1e300;
-    for (int p0 = 0; p0 < npairs; p0 += 64) {
-      const int pr = p0 + ll;
+    for (int w0 = 0; w0 < nwork; w0 += 64) {
+      const int w = w0 + ll;
       int cnt = 0, bi = 0, bj = 1;
       Pt pt0, pt1;
       pt0.n = v2(0, 0); pt0.p1 = pt0.n; pt0.p2 = pt0.n; pt0.pen = 0; pt1 = pt0;
-      if (pr < npairs) {
-        int rem = pr;                                           // pair index -> (i, j), i < j, lexicographic
-        while (rem >= nb - 1 - bi) { rem -= nb - 1 - bi; ++bi; }
-        bj = bi + 1 + rem;
-        const bool skip = P.no_contact && P.no_contact[((size_t)scene * nb + bi) * nb + bj];
-        if (!skip) {
-          Body b1, b2;
-          b1.kind = s_kind[bi]; b2.kind = s_kind[bj];
-          b1.pos = v2(s_pose[bi * 3 + 1], s_pose[bi * 3 + 2]); b2.pos = v2(s_pose[bj * 3 + 1], s_pose[bj * 3 + 2]);
-          b1.rad = s_rad[bi]; b2.rad = s_rad[bj];
-          const int o1 = s_off[bi], o2 = s_off[bj];
-          b1.nv = s_off[bi + 1] - o1; b2.nv = s_off[bj + 1] - o2;
-          b1.verts = s_verts + o1; b2.verts = s_verts + o2;
-          b1.nrm = s_nrm + o1; b2.nrm = s_nrm + o2; b1.elen = s_elen + o1; b2.elen = s_elen + o2;
-          cnt = collide_pair(b1, b2, P.eps, pt0, pt1);
+      bool run = w < nwork;
+      if (run) {
+        if constexpr (BP) {                                     // (the cull has looked at no_contact)
+          const int code = s_cull.cand[w];
+          bi = code >> 8; bj = code & 255;
+        } else {
+          pair_of(w, nb, bi, bj);
+          run = !(P.no_contact && P.no_contact[((size_t)scene * nb + bi) * nb + bj]);
         }
       }
-      // exclusive prefix sum of cnt over the wave (pair order = the reference's contact order)
-      int incl = cnt;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) { const int o = __shfl_up(incl, off, 64); if (ll >= off) incl += o; }
-      const int excl = incl - cnt;
-      const int total = __shfl(incl, 63, 64);
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        const Pt& pt = q == 0 ? pt0 : pt1;
-        const int slot = base + excl + q;
-        if (q < cnt && slot < P.maxc) {
-          const size_t o = (size_t)scene * P.maxc + slot;
-          P.c_n[o * 2] = (float)pt.n.x; P.c_n[o * 2 + 1] = (float)pt.n.y;
-          P.c_p1[o * 2] = (float)pt.p1.x; P.c_p1[o * 2 + 1] = (float)pt.p1.y;
-          P.c_p2[o * 2] = (float)pt.p2.x; P.c_p2[o * 2 + 1] = (float)pt.p2.y;
-          if (P.c_pen) P.c_pen[o] = pt.pen;
-          P.c_i1[o] = bi; P.c_i2[o] = bj;
-        }
-        if (q < cnt) maxpen = pt.pen > maxpen ? pt.pen : maxpen;
+      if (run) {
+        Body b1, b2;
+        b1.kind = s_kind[bi]; b2.kind = s_kind[bj];
+        b1.pos = v2(s_pose[bi * 3 + 1], s_pose[bi * 3 + 2]); b2.pos = v2(s_pose[bj * 3 + 1], s_pose[bj * 3 + 2]);
+        b1.rad = s_rad[bi]; b2.rad = s_rad[bj];
+        const int o1 = s_off[bi], o2 = s_off[bj];
+        b1.nv = s_off[bi + 1] - o1; b2.nv = s_off[bj + 1] - o2;
+        b1.verts = s_verts + o1; b2.verts = s_verts + o2;
+        b1.nrm = s_nrm + o1; b2.nrm = s_nrm + o2; b1.elen = s_elen + o1; b2.elen = s_elen + o2;
+        cnt = collide_pair(b1, b2, P.eps, pt0, pt1);
       }
-      base += total;
+      base += store_records(P, scene, ll, base, cnt, bi, bj, pt0, pt1, maxpen);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { const double o = __shfl_xor(maxpen, off, 64); maxpen = o > maxpen ? o : maxpen; }
+    maxpen = scene_max(maxpen);
     ++trial;
-    // world.py:95-101
-    const bool ok = !(base > 0 && maxpen > P.tol);
-    if (ok || (!P.strict && dt < P.dt_floor) || trial >= P.max_trials || !P.v || finished) done = true;   // (max_trials: the reference would spin)
-    else dt *= 0.5;
+    const bool done = accept_or_halve(P, base, maxpen, trial, finished, dt);
     if (__all(done)) break;
     __syncthreads();
   }
-  // pad the unused contact slots with a harmless record (no normal, bodies 0/0)
-  const int nfill = base < P.maxc ? base : P.maxc;
-  for (int slot = nfill + ll; slot < P.maxc; slot += 64) {
-    const size_t o = (size_t)scene * P.maxc + slot;
-    P.c_n[o * 2] = 0; P.c_n[o * 2 + 1] = 0; P.c_p1[o * 2] = 0; P.c_p1[o * 2 + 1] = 0; P.c_p2[o * 2] = 0; P.c_p2[o * 2 + 1] = 0;
-    if (P.c_pen) P.c_pen[o] = 0;
-    P.c_i1[o] = 0; P.c_i2[o] = 0;
-  }
-  if (P.p_out) for (int idx = ll; idx < nb * 3; idx += 64) P.p_out[(size_t)scene * nb * 3 + idx] = s_pose[idx];
-  if (ll == 0) {
-    P.count[scene] = base;                                  // may exceed maxc: the caller checks
-    if (P.max_pen) P.max_pen[scene] = base > 0 ? maxpen : 0.0;
-    if (P.dt_used) P.dt_used[scene] = finished ? 0.0 : dt;
-    if (P.t && !finished) P.t[scene] += dt;                              // world.py:122
-    if (P.trials) P.trials[scene] = trial;
-  }
+  scene_outputs(P, scene, ll, s_pose, base, maxpen, dt, trial, finished);
+  if (BP && ll == 0 && candidates) candidates[scene] = nwork;       // pairs that passed the cull at the accepted pose
 }
 
 // ---------------------------------------------------------------- backward of the contact frame
@@ -227,64 +194,13 @@ __global__ void __launch_bounds__(FB_T) lcp_contact_frame_backward_wide_kernel(i
   const int tid = threadIdx.x;
   const int scene = blockIdx.x;
   double* out = dp + (size_t)scene * nb * 3;
-  int ntot = count[scene];
-  ntot = ntot < 0 ? 0 : (ntot > maxc ? maxc : ntot);
   const int vtot = stage_bodies(scene, nb, nvcap, kind, nverts, radius, s_kind, s_off, s_rad);   // (uniform over the workgroup)
   if (vtot > vmax) {                                                  // scene_verts_max too small: no derivative
     for (int i = tid; i < nb * 3; i += FB_T) out[i] = 0.0;
     return;
   }
-  for (int i = tid; i < nb * 3; i += FB_T) s_pose[i] = p[(size_t)scene * nb * 3 + i];
-  // the work units: wave 0 flags the records that start a pair and compacts their indices with a ballot
-  if (tid < 64) {
-    int nu = 0;
-    for (int r0 = 0; r0 < ntot; r0 += 64) {
-      const int r = r0 + tid;
-      int i1 = 0, i2 = 0;
-      bool start = false;
-      if (r < ntot) {
-        const size_t o = (size_t)scene * maxc + r;
-        i1 = c_i1[o]; i2 = c_i2[o];
-        start = r == 0 || i1 != c_i1[o - 1] || i2 != c_i2[o - 1];
-        i1 = i1 < 0 ? 0 : (i1 >= nb ? nb - 1 : i1); i2 = i2 < 0 ? 0 : (i2 >= nb ? nb - 1 : i2);   // (body indices stay in the table)
-      }
-      const uint64_t m = __ballot(start);
-      if (start) {
-        const int u = nu + __popcll(m & ((1ull << tid) - 1));
-        s_ustart[u] = r; s_ub1[u] = i1; s_ub2[u] = i2;
-      }
-      nu += __popcll(m);
-    }
-    if (tid == 0) { s_ustart[nu] = ntot; s_nunits = nu; }
-  }
-  __syncthreads();
-  for (int b = tid; b < nb; b += FB_T) { const double rot = s_pose[b * 3]; s_sc[b] = make_double2(sin(rot), cos(rot)); }
-  __syncthreads();
-  // rotated vertices (the detection kernel's arithmetic: the same values, hence the same branches)
-  for (int b = 0; b < nb; ++b) {
-    const int o = s_off[b], n = s_off[b + 1] - o;
-    const double* vl = verts_local + ((size_t)scene * nb + b) * nvcap * 2;
-    const double sn = s_sc[b].x, cs = s_sc[b].y;
-    for (int k = tid; k < n; k += FB_T) {
-      const double lx = vl[2 * k], ly = vl[2 * k + 1];
-      s_verts[o + k] = make_double2(cs * lx - sn * ly, sn * lx + cs * ly);          // utils.py:105-112
-    }
-  }
-  __syncthreads();
-  for (int b = 0; b < nb; ++b) {
-    const int o = s_off[b], n = s_off[b + 1] - o;
-    for (int k = tid; k < n; k += FB_T) {
-      const V2 a = v2(s_verts[o + k].x, s_verts[o + k].y);
-      const V2 c = v2(s_verts[o + (k + 1) % n].x, s_verts[o + (k + 1) % n].y);
-      const V2 edge = c - a;
-      const double en = norm(edge);
-      const V2 nr = left_orth(edge) * (1.0 / en);
-      s_elen[o + k] = en;
-      s_nrm[o + k] = make_double2(nr.x, nr.y);
-    }
-  }
-  __syncthreads();
-  const int nunits = s_nunits;
+  const int nunits = stage_frame_scene<FB_T>(scene, nb, maxc, nvcap, verts_local, p, count, c_i1, c_i2, s_off, s_pose, s_sc, s_verts, s_nrm,
+                                             s_elen, s_ustart, s_ub1, s_ub2, &s_nunits);
   for (int w = tid; w < nunits * 6; w += FB_T) {
     using ad::Dual;
     const int u = w / 6, s = w - u * 6;
@@ -343,8 +259,15 @@ bool contacts_wide_supported(int nb, int nvcap, int scene_verts_max) {
 int contacts_wide_launch(const ContactArgs& P, int nvcap, int scene_verts_max, void* stream) {
   if (!contacts_wide_supported(P.nb, nvcap, scene_verts_max)) return LCP_E_TOOLARGE;
   const int vmax = ctw::vmax_of(scene_verts_max);
-  const auto kernel = P.dt_in ? ctw::lcp_move_find_contacts_wide_kernel<true> : ctw::lcp_move_find_contacts_wide_kernel<false>;
-  return ctw::launch_per_scene(kernel, P.B, 64, ctw::detect_lds(vmax), stream, P, nvcap, vmax);
+  const auto kernel = P.dt_in ? ctw::lcp_move_find_contacts_wide_kernel<true, false> : ctw::lcp_move_find_contacts_wide_kernel<false, false>;
+  return ctw::launch_per_scene(kernel, P.B, 64, ctw::detect_lds(vmax), stream, P, nvcap, vmax, (int32_t*)nullptr);
+}
+
+int contacts_bp_launch(const ContactArgs& P, int nvcap, int scene_verts_max, int32_t* candidates, void* stream) {
+  if (!contacts_wide_supported(P.nb, nvcap, scene_verts_max)) return LCP_E_TOOLARGE;
+  const int vmax = ctw::vmax_of(scene_verts_max);
+  const auto kernel = P.dt_in ? ctw::lcp_move_find_contacts_wide_kernel<true, true> : ctw::lcp_move_find_contacts_wide_kernel<false, true>;
+  return ctw::launch_per_scene(kernel, P.B, 64, ctw::detect_lds(vmax), stream, P, nvcap, vmax, candidates);
 }
 
 int contact_frame_backward_wide_launch(int B, int nb, int maxc, int nvcap, int scene_verts_max, const int32_t* kind,

@@ -245,7 +245,7 @@ int contact_frame_backward_wide_launch(int B, int nb, int maxc, int nvcap, int s
                                        double eps, const int32_t* count, const int32_t* c_i1, const int32_t* c_i2,
                                        const float* g_n, const float* g_p1, const float* g_p2, double* dp, void* stream);
 // the detection loop of contacts_wide_launch with a broadphase (bounding circle + box, survivors compacted in pair order) in front
-// of the narrow phase; candidates[B] or NULL: the pairs that passed at the accepted pose - lcp_contacts_bp.hip
+// of the narrow phase; candidates[B] or NULL: the pairs that passed at the accepted pose - lcp_contacts_wide.hip (the cull: lcp_contacts_bp.hip)
 int contacts_bp_launch(const ContactArgs& P, int nvcap, int scene_verts_max, int32_t* candidates, void* stream);
 // the reference's body constructors (bodies.py:15-290, forces.py:51-67): centroid, recentred vertices, inertia, mass matrix
 // diagonal and gravity from the raw shape and the mass, and their chain rule - lcp_bodies.hip (cap rounded up to a power of two

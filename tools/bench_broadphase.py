@@ -1,5 +1,5 @@
-"""Detection with and without the broadphase (lcp_contacts_bp.hip against the all-pairs kernels) on one GPU: `--batch` scenes of a
-floor and nb - 1 circles, rects and n-gons in columns of 8 (the piles of tools/bench_wide_contacts.py; 16 seeded scenes tiled over
+"""Detection with and without the broadphase (the detection kernel of lcp_contacts_wide.hip with the cull of lcp_contacts_bp.hip
+against the all-pairs kernels) on one GPU: `--batch` scenes of a floor and nb - 1 circles, rects and n-gons in columns of 8 (the piles of tools/bench_wide_contacts.py; 16 seeded scenes tiled over
 the batch), for nb = 12 and 20 (8-gons at capacity 8: the all-pairs side is lcp_contacts.hip, the kernel those sizes run on by
 default) and nb = 48 (16-gons at capacity 16: lcp_contacts_wide.hip, the shape of profiles/r07_wide_contacts.json).  Two launches
 are timed per size:

@@ -5,7 +5,10 @@ Without `--case`: the fused step on a seeded stack batch.  `--case NAME[,NAME...
 and every gradient of the workgroup-per-scene kernels (lcp_primal_wg.hip, tag 13; lcp_primal_wg_poststab.hip, tag 14) on B = 8
 stack scenes under path "primal_wg", at the pivot counts where the shared LU and sweeps change shape (all pivots in the first lane
 half, the lane split at 64, the capacity).  `--diff` prints the largest difference per tensor and, per case, whether every tensor
-is bitwise equal; it exits 1 when one is not."""
+is bitwise equal; it exits 1 when one is not.
+`--case contacts` (all of CONTACT_CASES): every output of find_contacts, move_and_find_contacts, contact_frame_backward and
+contact_frame_backward_shape on B = 8 seeded piles of tools/bench_wide_contacts.py::pile_scene, per body count, vertex capacity and
+broadphase setting - the sizes at which the parts the contact kernels share change behaviour (see contacts_case)."""
 import sys
 
 import torch
@@ -96,6 +99,85 @@ def wg_case(name):
     return res
 
 
+# name: (bodies, vertex capacity, broadphase).  nb 2: one pair; 12: 66 pairs, two passes of 64; 40: 780 pairs; 64: the body cap, 2016
+# pairs.  Capacity 8 with at most 32 bodies and no broadphase is served by lcp_contacts.hip, everything else by lcp_contacts_wide.hip.
+CONTACT_CASES = {"contacts_nb%d_cap%d%s" % (nb, cap, "_bp" if bp else ""): (nb, cap, bp)
+                 for nb in (2, 12, 40, 64) for cap in (8, 16, 64) for bp in (False, True)}
+
+
+def contacts_case(name):
+    """One case of CONTACT_CASES: dict of CPU tensors.  Eight different piles, pressed together until neighbours are 0.05 apart (inside
+    the detection margin), and these runs: `find` (detection at that pose); `move` (the move / halve loop from one dt, strict: velocities
+    that overshoot, so several halvings); `dts` (per-scene dt, not strict: scene 1 finished at dt = 0, scene 2 at dt < 0, scene 3 from a
+    dt eight times larger); `nc` (a no_contact mask); `small` (maxc below the list: count > maxc); `svm` (scene_verts_max one below the
+    largest scene: count = -1 there on the kernels that look at it); the frame backward for the pose and for the shape on `find`, `small`
+    and `svm`."""
+    import numpy as np
+    from lcp_physics_amd.physics import contacts as ct
+    from tools.bench_wide_contacts import pile_scene
+    nb, cap, bp = CONTACT_CASES[name]
+    B, dev = 8, torch.device("cuda")
+    geoms, poses = [], []
+    for b in range(B):
+        shapes, pose = pile_scene(np.random.default_rng(9000 + 100 * nb + b), nb, nv=min(cap, 16))
+        pose[1:, 2] += 0.15 * (1 + (np.arange(1, nb) - 1) % 8)            # (columns of 8: the k-th body above the floor comes down 0.15 k)
+        geoms.append(ct.GeometryBatch.from_shapes(shapes, 1, max_verts=cap))
+        poses.append(pose)
+    cat = lambda f: torch.cat([getattr(g, f) for g in geoms])
+    gen = torch.Generator().manual_seed(nb * 100 + cap)
+    mask = (torch.rand(B, nb, nb, generator=gen) < 0.15).to(torch.uint8)
+
+    def geometry(no_contact=None, svm=None):
+        return ct.GeometryBatch(cat("kind"), cat("radius"), cat("verts_local"), cat("nverts"), no_contact,
+                                max(g.scene_verts_max for g in geoms) if svm is None else svm).to(dev)
+
+    geom = geometry()
+    p = torch.tensor(np.stack(poses), dtype=torch.float64, device=dev)
+    v = (torch.randn(B, nb, 3, generator=gen) * torch.tensor([0.3, 5.0, 5.0])).float()
+    v[:, 1:, 2] += 30.0
+    v[:, 0] = 0.0
+    v = v.to(dev)
+    dt = 1.0 / 30
+    dts = torch.full((B,), dt, dtype=torch.float64)
+    dts[1], dts[2], dts[3], dts[4] = 0.0, -1.0, 8 * dt, dt / 16
+    maxc = 4 * nb
+    res = {}
+
+    def keep(run, cb, cand):
+        for k in ("p_out", "c_pen", "max_pen", "dt_used", "c_n", "c_p1", "c_p2", "c_i1", "c_i2", "count", "trials"):
+            res[run + "." + k] = getattr(cb, k).cpu()
+        if cand is not None:
+            res[run + ".candidates"] = cand.cpu()
+
+    def detect(run, g, maxc_, **kw):
+        cand = torch.full((B,), -7, dtype=torch.int32, device=dev) if bp else None
+        cb = ct.move_and_find_contacts(g, p, kw.pop("v", None), kw.pop("dt", 0.0), maxc=maxc_, broadphase=bp, candidates=cand, **kw)
+        keep(run, cb, cand)
+        return cb
+
+    def backward(run, g, cb):
+        gs = [torch.randn(B, cb.c_n.shape[1], 2, generator=gen).to(dev) for _ in range(3)]
+        res[run + ".dp"] = ct.contact_frame_backward(g, p, cb, *gs).cpu()
+        d_rad, d_verts = ct.contact_frame_backward_shape(g, p, cb, *gs)
+        res[run + ".d_radius"], res[run + ".d_verts_local"] = d_rad.cpu(), d_verts.cpu()
+
+    found = detect("find", geom, maxc, max_trials=1)
+    backward("find", geom, found)
+    moved = detect("move", geom, maxc, v=v, dt=dt, strict=True)
+    stepped = detect("dts", geom, maxc, v=v, dt=dt, strict=False, dt_scene=dts.to(dev))
+    detect("nc", geometry(no_contact=mask), maxc, v=v, dt=dt, strict=True)
+    nmax = int(found.count.max())
+    small = detect("small", geom, max(1, nmax // 2), max_trials=1)
+    backward("small", geom, small)
+    short = geometry(svm=max(0, geom.scene_verts_max - 1))
+    cut = detect("svm", short, maxc, max_trials=1)
+    backward("svm", short, cut)
+    torch.cuda.synchronize()
+    print(name, "contacts", found.count.tolist(), "trials move", moved.trials.tolist(), "trials dts", stepped.trials.tolist(), "count small",
+          small.count.tolist(), "maxc small", small.maxc, "count svm", cut.count.tolist(), "tensors", len(res))
+    return res
+
+
 def diff(fa, fb):
     a, b = torch.load(fa), torch.load(fb)
     assert set(a) == set(b), (sorted(a), sorted(b))
@@ -115,10 +197,10 @@ def main():
     if sys.argv[1] == "--diff":
         sys.exit(0 if diff(sys.argv[2], sys.argv[3]) else 1)
     if sys.argv[1] == "--case":
-        names = list(WG_CASES) if sys.argv[2] == "wg" else sys.argv[2].split(",")
+        names = {"wg": list(WG_CASES), "contacts": list(CONTACT_CASES)}.get(sys.argv[2]) or sys.argv[2].split(",")
         res = {}
         for name in names:
-            res.update({name + "/" + k: v for k, v in wg_case(name).items()})
+            res.update({name + "/" + k: v for k, v in (contacts_case if name in CONTACT_CASES else wg_case)(name).items()})
         torch.save(res, sys.argv[3])
         return
     from lcp_physics_amd.physics.batched_world import fused_step
