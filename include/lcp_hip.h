@@ -564,8 +564,8 @@ int lcp_body_properties_backward_f64(int B, int nb, int cap, const int32_t* kind
  * What Body.draw paints (physics/bodies.py:140-150 circles, :237-250 hulls: pixel = pos * pixels_per_meter, x to the right, y
  * downward, thickness 0 = filled, > 0 = an outline) in the order of the paint loop of run_world (world.py:279-280: list order,
  * later over earlier), for B scenes in one launch (lcp_render.hip) - what Recorder (utils.py:54-72) and
- * run_world(screen=, recorder=) (world.py:246-320) need of the world state, as tensors.  Not drawn: the circle's spoke, the
- * hull's centre dot, the joints' markers, a hull of fewer than three vertices.
+ * run_world(screen=, recorder=) (world.py:246-320) need of the world state, as tensors.  Not drawn: a hull of fewer than three
+ * vertices.  The circle's spoke, the hull's centre dot, the rect's diagonals and the joints' markers: lcp_render_marks_f64 below.
  *   camera: H x W pixels, pixel (i, j) sampled at x = (x0 + (j + 1/2) / ppm, y0 + (i + 1/2) / ppm); w > 0: the width of the edge
  *       ramp in world units (one pixel: 1 / ppm).
  *   signed distance d_k(x): circle |x - c| - r; hull with w_i = c + R(rot) v_i (utils.py:105-112), e_i = w_i+1 - w_i,
@@ -602,6 +602,74 @@ int lcp_render_backward_f64(int B, int nb, int nvcap, int scene_verts_max, int H
                             const double* p, const float* colors, const float* background, const double* thickness,
                             double x0, double y0, double ppm, double w, const float* g_image,
                             double* g_p, double* g_radius, double* g_verts_local, float* g_colors, void* stream);
+
+/* The same frames with the marks Body.draw puts on the bodies and the joints' markers, the rest of run_world's paint loop
+ * (world.py:279-282), in one launch (lcp_render_marks.hip).  Every convention of lcp_render_f64 holds: pixel centres, cov, the
+ * compositing I = I (1 - alpha) + alpha colour back to front, fp64 arithmetic, fp32 image.  A frame is an ordered list of LAYERS:
+ * the bodies' are exactly those of lcp_render_f64, the new ones are built from two primitives:
+ *   segment (A, B, width s): d = dist(x, segment AB) - s / 2, alpha = cov(d).  A == B is the point A: the projection parameter is
+ *       0 and nothing is divided by |AB|^2.  Where dist = 0 the direction dd/dx is 0 (as at a circle's centre).
+ *   disc / ring (A, radius r, thickness t): d = |x - A| - r; filled: alpha = cov(d); ring: alpha = cov(d) - cov(d + t).
+ * Body marks, mark[B,nb] i32 (NULL: none), colours mark_colors[B,nb,C] f32 (required with mark):
+ *       0 none
+ *       1 SPOKE      segment c -> c + rad (cos rot, sin rot), width line_w            circles only        bodies.py:144-147
+ *       2 CENTRE     filled disc at c, radius dot_r                                   any kind            bodies.py:245-247
+ *       3 DIAGONALS  segments w0 - w2 and w1 - w3 of the world vertices, width line_w hulls, nverts == 4  bodies.py:295-296
+ *   A code that does not fit its body (a spoke on a hull, diagonals on a hull of nverts != 4, any other code) is not drawn:
+ *   alpha = 0 and no gradient.
+ * Joint markers, painted after all bodies, joint 0 first; jtype, jb1, jb2 [B,nj] i32, jr1, jrot1 [B,nj] f64 (the layout of
+ * lcp_joint_jacobian_f64, read per scene), joint_colors[B,nj,C] f32; 0 <= nj <= 64, every joint pointer may be NULL when nj == 0:
+ *       JOINT   filled disc, radius dot_r, at c_b1 + jr1 (cos jrot1, sin jrot1)                      constraints.py:44-53
+ *       FIXED   segment c_b1 -> c_b2, width joint_w; not drawn when jb2 < 0                          constraints.py:89-92
+ *       YCON    horizontal tick c_b1 -+ (joint_r, 0), width joint_w                                  constraints.py:117-119
+ *       XCON    vertical tick c_b1 -+ (0, joint_r), width joint_w                                    constraints.py:144-146
+ *       ROTCON  ring at c_b1, radius joint_r, thickness line_w                                       constraints.py:171-173
+ *       TOTAL   that ring, then the horizontal tick, then the vertical tick                          constraints.py:202-206
+ *   A joint of any other type, or whose body index lies outside [0, nb), is not drawn.  The lengths are world lengths (the
+ *   reference's pixel constants divided by pixels_per_meter: line_w 1, dot_r 2, joint_w 2, joint_r 5 pixels).
+ * order = 0, the reference's: for each body k its SPOKE or DIAGONALS under body k, then body k, then its CENTRE over it; then the
+ *       joints.  order = 1: for each body k the body, then its mark whatever the code; then the joints (a filled body hides a
+ *       mark painted under it, as pygame would).
+ * ids is unchanged by marks and markers: the topmost filled body silhouette.
+ * Not reproduced: the reference's one-pixel offset of the TOTAL marker's ring (constraints.py:203); its integer pixel rounding
+ * of every coordinate; a hull of fewer than three vertices (its CENTRE mark is drawn).
+ * Sizes and checks of lcp_render_f64, and: 0 <= nj <= 64, order in {0, 1}, line_w > 0, joint_w > 0, dot_r >= 0, joint_r >= 0,
+ * mark_colors with mark, every joint array with nj > 0 - anything else is LCP_E_BADARG before any launch.  The tile mapping of
+ * lcp_render_f64; every layer is culled by a bounding circle grown by w / 2 and the rounding slack, where its alpha is exactly 0.
+ * No allocation, no synchronisation, no global state. */
+int lcp_render_marks_f64(int B, int nb, int nvcap, int scene_verts_max, int H, int W, int C,
+                         const int32_t* kind, const double* radius, const double* verts_local, const int32_t* nverts,
+                         const double* p, const float* colors, const float* background, const double* thickness,
+                         double x0, double y0, double ppm, double w,
+                         const int32_t* mark, const float* mark_colors,
+                         int nj, const int32_t* jtype, const int32_t* jb1, const int32_t* jb2, const double* jr1, const double* jrot1,
+                         const float* joint_colors,
+                         int order, double line_w, double dot_r, double joint_w, double joint_r,
+                         float* image, int32_t* ids, void* stream);
+
+/* Backward of the image of lcp_render_marks_f64.  Same inputs and checks; nothing is saved by the forward.
+ *   in: g_image[B,C,H,W] f32 (required).
+ *   out (each optional, at least one; written, never accumulated): g_p[B,nb,3] f64, g_radius[B,nb] f64 (hulls: 0),
+ *       g_verts_local[B,nb,nvcap,2] f64 (body frame; circles and slots >= nverts: 0), g_colors[B,nb,C] f32,
+ *       g_mark_colors[B,nb,C] f32 (undrawn marks: 0), g_joint_colors[B,nj,C] f32, g_jrot1[B,nj] f64, g_jr1[B,nj] f64 (joints other
+ *       than JOINT: 0).
+ *   workspace: g_p_joints[B,nj,2,3] f64, required when g_p is asked for and nj > 0 (LCP_E_BADARG without it): every joint's pull
+ *       on its two bodies, written by the first launch and added to g_p, body by body in joint order, by a second one.
+ * The spoke reaches rot, c and radius; the diagonals verts_local, rot and c; the centre dot c; the markers the positions of jb1 /
+ * jb2, jrot1 and jr1.  One workgroup per (scene, body) owns the body and its mark over the group's pixel box, one per (scene, joint)
+ * the joint's marker over its own, in ONE launch; the second launch (one thread per body) only when g_p is asked for and nj > 0.
+ * No atomics, sums in a fixed order: two runs give the same bits. */
+int lcp_render_marks_backward_f64(int B, int nb, int nvcap, int scene_verts_max, int H, int W, int C,
+                                  const int32_t* kind, const double* radius, const double* verts_local, const int32_t* nverts,
+                                  const double* p, const float* colors, const float* background, const double* thickness,
+                                  double x0, double y0, double ppm, double w,
+                                  const int32_t* mark, const float* mark_colors,
+                                  int nj, const int32_t* jtype, const int32_t* jb1, const int32_t* jb2, const double* jr1,
+                                  const double* jrot1, const float* joint_colors,
+                                  int order, double line_w, double dot_r, double joint_w, double joint_r,
+                                  const float* g_image,
+                                  double* g_p, double* g_radius, double* g_verts_local, float* g_colors, float* g_mark_colors,
+                                  float* g_joint_colors, double* g_jrot1, double* g_jr1, double* g_p_joints, void* stream);
 
 /* ---- the breakout encoder: frames -> paddle, blocks and ball of every scene ----
  * What extract_params (experiments/breakout/encoder.py:63-133, with remove_rect :136-137 and get_pos_dims :140-145) reads off

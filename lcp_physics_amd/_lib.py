@@ -81,6 +81,11 @@ SIGNATURES = {
     "lcp_body_properties_backward_f64": (_I, [_I] * 3 + [_P] * 5 + [_c.c_double] + [_P] * 5 + [_P] * 3 + [_P]),
     "lcp_render_f64": (_I, [_I] * 7 + [_P] * 8 + [_c.c_double] * 4 + [_P, _P] + [_P]),
     "lcp_render_backward_f64": (_I, [_I] * 7 + [_P] * 8 + [_c.c_double] * 4 + [_P] + [_P] * 4 + [_P]),
+    # the marks and markers: mark, mark_colors, nj, jtype, jb1, jb2, jr1, jrot1, joint_colors, order, line_w, dot_r, joint_w, joint_r
+    "lcp_render_marks_f64": (_I, [_I] * 7 + [_P] * 8 + [_c.c_double] * 4 + [_P, _P, _I] + [_P] * 6 + [_I] + [_c.c_double] * 4
+                             + [_P, _P] + [_P]),
+    "lcp_render_marks_backward_f64": (_I, [_I] * 7 + [_P] * 8 + [_c.c_double] * 4 + [_P, _P, _I] + [_P] * 6 + [_I]
+                                      + [_c.c_double] * 4 + [_P] + [_P] * 9 + [_P]),
     "lcp_extract_params_u8": (_I, [_I] * 3 + [_P] + [_c.c_int64] * 3 + [_P, _I] + [_P] * 8 + [_P]),
     "lcp_joint_jacobian_backward_f64": (_I, [_I] * 4 + [_P] * 6 + [_P, _P, _P]),
     "lcp_state_update_backward_f64": (_I, [_I] * 3 + [_P] * 5 + [_c.c_double] + [_P] * 3 + [_P]),

@@ -762,6 +762,54 @@ int lcp_render_backward_f64(int B, int nb, int nvcap, int scene_verts_max, int H
                                      thickness, x0, y0, ppm, w, g_image, g_p, g_radius, g_verts_local, g_colors, stream);
 }
 
+// what the two entries with marks and markers refuse on top of render_args_ok: a joint count outside 0..64, an order other than 0 / 1,
+// a width that is not positive, a negative radius (a NaN fails either), marks without colours, joints without one of their arrays
+static bool render_marks_ok(const int32_t* mark, const float* mark_colors, int nj, const void* jtype, const void* jb1, const void* jb2,
+                            const void* jr1, const void* jrot1, const void* joint_colors, int order, double line_w, double dot_r,
+                            double joint_w, double joint_r) {
+  if (nj < 0 || nj > 64 || (order != 0 && order != 1)) return false;
+  if (!(line_w > 0.0) || !(joint_w > 0.0) || !(dot_r >= 0.0) || !(joint_r >= 0.0)) return false;
+  if (mark && !mark_colors) return false;
+  return nj == 0 || (jtype && jb1 && jb2 && jr1 && jrot1 && joint_colors);
+}
+
+int lcp_render_marks_f64(int B, int nb, int nvcap, int scene_verts_max, int H, int W, int C, const int32_t* kind, const double* radius,
+                         const double* verts_local, const int32_t* nverts, const double* p, const float* colors, const float* background,
+                         const double* thickness, double x0, double y0, double ppm, double w, const int32_t* mark,
+                         const float* mark_colors, int nj, const int32_t* jtype, const int32_t* jb1, const int32_t* jb2, const double* jr1,
+                         const double* jrot1, const float* joint_colors, int order, double line_w, double dot_r, double joint_w,
+                         double joint_r, float* image, int32_t* ids, void* stream) {
+  if (!render_args_ok(B, nb, nvcap, scene_verts_max, H, W, C, kind, radius, verts_local, nverts, p, colors, background, ppm, w))
+    return LCP_E_BADARG;
+  if (!render_marks_ok(mark, mark_colors, nj, jtype, jb1, jb2, jr1, jrot1, joint_colors, order, line_w, dot_r, joint_w, joint_r))
+    return LCP_E_BADARG;
+  if (!image && !ids) return LCP_E_BADARG;                            // (nothing asked for)
+  const lcp::RenderMarks mk{mark, mark_colors, nj, jtype, jb1, jb2, jr1, jrot1, joint_colors, order, line_w, dot_r, joint_w, joint_r};
+  return lcp::render_marks_launch(B, nb, nvcap, scene_verts_max, H, W, C, kind, radius, verts_local, nverts, p, colors, background,
+                                  thickness, x0, y0, ppm, w, mk, image, ids, stream);
+}
+
+int lcp_render_marks_backward_f64(int B, int nb, int nvcap, int scene_verts_max, int H, int W, int C, const int32_t* kind,
+                                  const double* radius, const double* verts_local, const int32_t* nverts, const double* p,
+                                  const float* colors, const float* background, const double* thickness, double x0, double y0, double ppm,
+                                  double w, const int32_t* mark, const float* mark_colors, int nj, const int32_t* jtype, const int32_t* jb1,
+                                  const int32_t* jb2, const double* jr1, const double* jrot1, const float* joint_colors, int order,
+                                  double line_w, double dot_r, double joint_w, double joint_r, const float* g_image, double* g_p,
+                                  double* g_radius, double* g_verts_local, float* g_colors, float* g_mark_colors, float* g_joint_colors,
+                                  double* g_jrot1, double* g_jr1, double* g_p_joints, void* stream) {
+  if (!render_args_ok(B, nb, nvcap, scene_verts_max, H, W, C, kind, radius, verts_local, nverts, p, colors, background, ppm, w))
+    return LCP_E_BADARG;
+  if (!render_marks_ok(mark, mark_colors, nj, jtype, jb1, jb2, jr1, jrot1, joint_colors, order, line_w, dot_r, joint_w, joint_r))
+    return LCP_E_BADARG;
+  if (!g_image || (!g_p && !g_radius && !g_verts_local && !g_colors && !g_mark_colors && !g_joint_colors && !g_jrot1 && !g_jr1))
+    return LCP_E_BADARG;
+  if (g_p && nj > 0 && !g_p_joints) return LCP_E_BADARG;              // (the joints' pull on their bodies needs its workspace)
+  const lcp::RenderMarks mk{mark, mark_colors, nj, jtype, jb1, jb2, jr1, jrot1, joint_colors, order, line_w, dot_r, joint_w, joint_r};
+  return lcp::render_marks_backward_launch(B, nb, nvcap, scene_verts_max, H, W, C, kind, radius, verts_local, nverts, p, colors,
+                                           background, thickness, x0, y0, ppm, w, mk, g_image, g_p, g_radius, g_verts_local, g_colors,
+                                           g_mark_colors, g_joint_colors, g_jrot1, g_jr1, g_p_joints, stream);
+}
+
 // the layout words of lcp_extract_params_u8 against an H x W image (include/lcp_hip.h lists what is refused)
 static bool encoder_layout_ok(const int32_t* w, int H, int W) {
   const int paddle_line = w[0], paddle_h = w[1], paddle_w = w[2], paddle_key = w[3], ball_w = w[4], nrows = w[5], band_top = w[6],

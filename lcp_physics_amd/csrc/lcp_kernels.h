@@ -269,6 +269,24 @@ int render_backward_launch(int B, int nb, int nvcap, int scene_verts_max, int H,
                            double w, const float* g_image, double* g_p, double* g_radius, double* g_verts_local, float* g_colors,
                            void* stream);
 
+// lcp_render_marks.hip: the same frames with the bodies' marks (spoke, centre dot, diagonals) and the joints' markers
+// (bodies.py:144-147, 245-247, 295-296; constraints.py:51-206; world.py:281-282) and their backward; arguments checked by the caller
+struct RenderMarks {
+  const int32_t* mark; const float* mark_colors;                     // [B,nb], [B,nb,C]; mark NULL: none
+  int nj; const int32_t *jtype, *jb1, *jb2; const double *jr1, *jrot1; const float* joint_colors;      // the JointSet layout, [B,nj]
+  int order; double line_w, dot_r, joint_w, joint_r;
+};
+int render_marks_launch(int B, int nb, int nvcap, int scene_verts_max, int H, int W, int C, const int32_t* kind, const double* radius,
+                        const double* verts_local, const int32_t* nverts, const double* p, const float* colors, const float* background,
+                        const double* thickness, double x0, double y0, double ppm, double w, const RenderMarks& mk, float* image,
+                        int32_t* ids, void* stream);
+int render_marks_backward_launch(int B, int nb, int nvcap, int scene_verts_max, int H, int W, int C, const int32_t* kind,
+                                 const double* radius, const double* verts_local, const int32_t* nverts, const double* p,
+                                 const float* colors, const float* background, const double* thickness, double x0, double y0, double ppm,
+                                 double w, const RenderMarks& mk, const float* g_image, double* g_p, double* g_radius,
+                                 double* g_verts_local, float* g_colors, float* g_mark_colors, float* g_joint_colors, double* g_jrot1,
+                                 double* g_jr1, double* g_p_joints, void* stream);
+
 // lcp_encoder.hip: the breakout encoder (experiments/breakout/encoder.py:63-145), one workgroup per frame; arguments checked by
 // the caller, `layout` the LCP_ENC_LAYOUT_WORDS host words
 int extract_params_launch(int B, int H, int W, const uint8_t* frame, long long stride_b, long long stride_row, long long stride_col,

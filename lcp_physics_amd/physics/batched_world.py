@@ -1012,8 +1012,22 @@ class ContactWorld:
     def get_p(self):
         return self.p
 
-    def render(self, cam, colors, **kw):
+    def _joints_to_draw(self):
+        if self.joints is None:
+            raise ValueError("joints=True needs a world built with a JointSet")
+        return self.joints
+
+    def render(self, cam, colors, joints=False, **kw):
         """The current frame of every scene, `image [B,C,H,W]` float32 (`physics.render.render(self.geom, self.p, cam, colors, **kw)`:
-        Body.draw in the paint order of world.py:279-280).  After `step(differentiable=True)` the image is part of the roll-out's graph."""
+        Body.draw in the paint order of world.py:279-280).  After `step(differentiable=True)` the image is part of the roll-out's graph.
+        `joints=True` draws the markers of the world's `JointSet` (world.py:281-282; `marks=` and the other keywords of `render` pass
+        through) - after differentiable steps at the joint angles the roll-out's graph holds, so a pixel loss reaches their history.
+        A `JointSet` given as `joints` is drawn as it is."""
         from .render import render
-        return render(self.geom, self.p, cam, colors, **kw)
+        if joints is True:
+            joints = self._joints_to_draw()
+            if "jrot1" not in kw and self._jrot_ad is not None and self._jrot_src is self.p:
+                kw["jrot1"] = self._jrot_ad
+        elif joints is False:
+            joints = None
+        return render(self.geom, self.p, cam, colors, joints=joints, **kw)
