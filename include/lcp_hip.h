@@ -671,6 +671,53 @@ int lcp_render_marks_backward_f64(int B, int nb, int nvcap, int scene_verts_max,
                                   double* g_p, double* g_radius, double* g_verts_local, float* g_colors, float* g_mark_colors,
                                   float* g_joint_colors, double* g_jrot1, double* g_jr1, double* g_p_joints, void* stream);
 
+/* ---- range sensors: rays cast against every scene's geometry, differentiable ----
+ * A fan of rays mounted on a body (or on the world frame), each returning the distance to the first surface it meets, for B scenes
+ * in one launch (lcp_sensors.hip).  The scene inputs, their limits and the world vertices w_i, edges e_i = w_i+1 - w_i and outward
+ * normals n_i are exactly those of lcp_render_f64 (utils.py:105-112, contacts.py:229-231); a scene with more hull vertices than
+ * scene_verts_max is not sensed (every ray misses), a hull of fewer than three vertices is never hit.
+ *   rays, R per scene: ray_body[B,R] i32 (the mounting body m; -1: the world frame; any other value outside [0, nb): the ray misses),
+ *       ray_origin[B,R,2] f64 and ray_angle[B,R] f64 in the mounting frame, ray_range[B,R] f64 > 0.
+ *       o = c_m + R(rot_m) origin, u = (cos, sin)(rot_m + angle); world frame: o = origin, the angle as it is.  A ray never tests its
+ *       own mounting body.
+ *   per body k:
+ *       circle  q = o - c, b = q . u, cc = q . q - r^2.  cc <= 0: s = 0 (the origin inside or on it).  Otherwise a miss if b >= 0 or
+ *               b^2 - cc < 0; otherwise s = -b - sqrt(b^2 - cc), n = (o + s u - c) / r.
+ *       hull    h_i = n_i . (o - w_i), den_i = n_i . u.  All h_i <= 0: s = 0 (inside).  An edge with den_i == 0 and h_i > 0: a miss.
+ *               s_in = max of -h_i / den_i over the edges with den_i < 0 (the first i on ties), s_out = min of -h_i / den_i over those
+ *               with den_i > 0.  A hit iff 0 <= s_in <= s_out: s = s_in, n = that edge's normal, t = (o + s u - w_i) . e_i / |e_i|^2.
+ *   per ray: the smallest s_k, on ties the smallest k.  None, or s >= ray_range: dist = ray_range, hit = -1, normal = 0.
+ *   out (each optional, at least one; written, never accumulated): dist[B,R] f64, hit[B,R] i32, normal[B,R,2] f64 (0 for a miss and
+ *       for s = 0).
+ * Sizes: those of lcp_render_f64 (1 <= nb <= 64, 8 <= nvcap <= 64, 0 <= scene_verts_max <= 1024), 1 <= R <= 1024, B >= 0; a NULL
+ * scene or ray array, no output - anything else is LCP_E_BADARG before any launch.  B == 0: success, no launch.  fp64 arithmetic.  One
+ * workgroup per (scene, 256 rays), lane = ray; a body whose bounding circle none of a wavefront's rays can reach within their range is
+ * skipped by that wavefront, where the rule gives a miss or s >= ray_range.  No allocation, no synchronisation, no global state. */
+int lcp_cast_rays_f64(int B, int nb, int nvcap, int scene_verts_max, int R,
+                      const int32_t* kind, const double* radius, const double* verts_local, const int32_t* nverts, const double* p,
+                      const int32_t* ray_body, const double* ray_origin, const double* ray_angle, const double* ray_range,
+                      double* dist, int32_t* hit, double* normal, void* stream);
+
+/* Backward of dist of lcp_cast_rays_f64.  Same inputs and checks; nothing is saved by the forward, every ray's hit is recomputed.
+ *   in: g_dist[B,R] f64 (required).
+ *   out (each optional, at least one; written, never accumulated): g_p[B,nb,3] f64, g_radius[B,nb] f64 (hulls: 0),
+ *       g_verts_local[B,nb,nvcap,2] f64 (body frame; circles and slots >= nverts: 0), g_ray_origin[B,R,2] f64, g_ray_angle[B,R] f64.
+ * A hit with 0 < s < ray_range differentiates by
+ *       ds = (n . dX + dr - n . (do + s du)) / (n . u)
+ *   dX: the motion of the material surface point - a circle: dc; a hull: (1 - t) dw_i + t dw_i+1 with
+ *       dw = dc + drot perp(w - c) + R(rot) dv_local;  dr: the circle's radius (a hull: 0);
+ *   do = dc_m + drot_m perp(o - c_m) + R(rot_m) d(origin),  du = (drot_m + d(angle)) perp(u),  perp(x, y) = (-y, x).
+ * Misses, rays clamped at their range and hits with s = 0 have zero gradient.  A body collects from every ray that hits it and from
+ * every ray mounted on it: one workgroup per scene, the rays' terms staged in LDS, every body owned by one wavefront that sums over
+ * the rays in order - no atomics, two runs give the same bits. */
+int lcp_cast_rays_backward_f64(int B, int nb, int nvcap, int scene_verts_max, int R,
+                               const int32_t* kind, const double* radius, const double* verts_local, const int32_t* nverts,
+                               const double* p,
+                               const int32_t* ray_body, const double* ray_origin, const double* ray_angle, const double* ray_range,
+                               const double* g_dist,
+                               double* g_p, double* g_radius, double* g_verts_local, double* g_ray_origin, double* g_ray_angle,
+                               void* stream);
+
 /* ---- the breakout encoder: frames -> paddle, blocks and ball of every scene ----
  * What extract_params (experiments/breakout/encoder.py:63-133, with remove_rect :136-137 and get_pos_dims :140-145) reads off
  * an Atari Breakout frame, for B frames in one launch (lcp_encoder.hip).  The reference reads channel 0 only (`frame[..., 0]`):

@@ -86,6 +86,9 @@ SIGNATURES = {
                              + [_P, _P] + [_P]),
     "lcp_render_marks_backward_f64": (_I, [_I] * 7 + [_P] * 8 + [_c.c_double] * 4 + [_P, _P, _I] + [_P] * 6 + [_I]
                                       + [_c.c_double] * 4 + [_P] + [_P] * 9 + [_P]),
+    # the range sensors: sizes, the scene, the rays (body, origin, angle, range), then the outputs
+    "lcp_cast_rays_f64": (_I, [_I] * 5 + [_P] * 5 + [_P] * 4 + [_P] * 3 + [_P]),
+    "lcp_cast_rays_backward_f64": (_I, [_I] * 5 + [_P] * 5 + [_P] * 4 + [_P] + [_P] * 5 + [_P]),
     "lcp_extract_params_u8": (_I, [_I] * 3 + [_P] + [_c.c_int64] * 3 + [_P, _I] + [_P] * 8 + [_P]),
     "lcp_joint_jacobian_backward_f64": (_I, [_I] * 4 + [_P] * 6 + [_P, _P, _P]),
     "lcp_state_update_backward_f64": (_I, [_I] * 3 + [_P] * 5 + [_c.c_double] + [_P] * 3 + [_P]),

@@ -810,6 +810,40 @@ int lcp_render_marks_backward_f64(int B, int nb, int nvcap, int scene_verts_max,
                                            g_mark_colors, g_joint_colors, g_jrot1, g_jr1, g_p_joints, stream);
 }
 
+// what both ray entries refuse before any launch: a negative batch, sizes outside the packed vertex list's, a ray count outside
+// 1..1024, a missing scene or ray array
+static bool cast_rays_args_ok(int B, int nb, int nvcap, int scene_verts_max, int R, const void* kind, const void* radius,
+                              const void* verts_local, const void* nverts, const void* p, const void* ray_body, const void* ray_origin,
+                              const void* ray_angle, const void* ray_range) {
+  if (B < 0 || !lcp::cast_rays_supported(nb, nvcap, scene_verts_max, R)) return false;
+  return kind && radius && verts_local && nverts && p && ray_body && ray_origin && ray_angle && ray_range;
+}
+
+int lcp_cast_rays_f64(int B, int nb, int nvcap, int scene_verts_max, int R, const int32_t* kind, const double* radius,
+                      const double* verts_local, const int32_t* nverts, const double* p, const int32_t* ray_body,
+                      const double* ray_origin, const double* ray_angle, const double* ray_range, double* dist, int32_t* hit,
+                      double* normal, void* stream) {
+  if (!cast_rays_args_ok(B, nb, nvcap, scene_verts_max, R, kind, radius, verts_local, nverts, p, ray_body, ray_origin, ray_angle, ray_range))
+    return LCP_E_BADARG;
+  if (!dist && !hit && !normal) return LCP_E_BADARG;                  // (nothing asked for)
+  if (B == 0) return 0;
+  return lcp::cast_rays_launch(B, nb, nvcap, scene_verts_max, R, kind, radius, verts_local, nverts, p, ray_body, ray_origin, ray_angle,
+                               ray_range, dist, hit, normal, stream);
+}
+
+int lcp_cast_rays_backward_f64(int B, int nb, int nvcap, int scene_verts_max, int R, const int32_t* kind, const double* radius,
+                               const double* verts_local, const int32_t* nverts, const double* p, const int32_t* ray_body,
+                               const double* ray_origin, const double* ray_angle, const double* ray_range, const double* g_dist,
+                               double* g_p, double* g_radius, double* g_verts_local, double* g_ray_origin, double* g_ray_angle,
+                               void* stream) {
+  if (!cast_rays_args_ok(B, nb, nvcap, scene_verts_max, R, kind, radius, verts_local, nverts, p, ray_body, ray_origin, ray_angle, ray_range))
+    return LCP_E_BADARG;
+  if (!g_dist || (!g_p && !g_radius && !g_verts_local && !g_ray_origin && !g_ray_angle)) return LCP_E_BADARG;
+  if (B == 0) return 0;
+  return lcp::cast_rays_backward_launch(B, nb, nvcap, scene_verts_max, R, kind, radius, verts_local, nverts, p, ray_body, ray_origin,
+                                        ray_angle, ray_range, g_dist, g_p, g_radius, g_verts_local, g_ray_origin, g_ray_angle, stream);
+}
+
 // the layout words of lcp_extract_params_u8 against an H x W image (include/lcp_hip.h lists what is refused)
 static bool encoder_layout_ok(const int32_t* w, int H, int W) {
   const int paddle_line = w[0], paddle_h = w[1], paddle_w = w[2], paddle_key = w[3], ball_w = w[4], nrows = w[5], band_top = w[6],

@@ -287,6 +287,19 @@ int render_marks_backward_launch(int B, int nb, int nvcap, int scene_verts_max, 
                                  double* g_verts_local, float* g_colors, float* g_mark_colors, float* g_joint_colors, double* g_jrot1,
                                  double* g_jr1, double* g_p_joints, void* stream);
 
+// lcp_sensors.hip: rays cast against every scene's geometry (include/lcp_hip.h, "range sensors") and the backward of the distances;
+// arguments checked by the caller
+bool cast_rays_supported(int nb, int nvcap, int scene_verts_max, int R);          // render_supported and 1 <= R <= 1024
+int cast_rays_launch(int B, int nb, int nvcap, int scene_verts_max, int R, const int32_t* kind, const double* radius,
+                     const double* verts_local, const int32_t* nverts, const double* p, const int32_t* ray_body,
+                     const double* ray_origin, const double* ray_angle, const double* ray_range, double* dist, int32_t* hit,
+                     double* normal, void* stream);
+int cast_rays_backward_launch(int B, int nb, int nvcap, int scene_verts_max, int R, const int32_t* kind, const double* radius,
+                              const double* verts_local, const int32_t* nverts, const double* p, const int32_t* ray_body,
+                              const double* ray_origin, const double* ray_angle, const double* ray_range, const double* g_dist,
+                              double* g_p, double* g_radius, double* g_verts_local, double* g_ray_origin, double* g_ray_angle,
+                              void* stream);
+
 // lcp_encoder.hip: the breakout encoder (experiments/breakout/encoder.py:63-145), one workgroup per frame; arguments checked by
 // the caller, `layout` the LCP_ENC_LAYOUT_WORDS host words
 int extract_params_launch(int B, int H, int W, const uint8_t* frame, long long stride_b, long long stride_row, long long stride_col,

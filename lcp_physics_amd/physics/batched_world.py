@@ -1031,3 +1031,10 @@ class ContactWorld:
         elif joints is False:
             joints = None
         return render(self.geom, self.p, cam, colors, joints=joints, **kw)
+
+    def sense(self, rays, **kw):
+        """The range readings of every scene, `dist [B,R]` f64 and `hit [B,R]` int32 (`physics.sensors.cast_rays(self.geom, self.p,
+        rays, **kw)`; `normals=True` adds the surface normals), at the pose `render` draws.  After `step(differentiable=True)` the
+        distances are part of the roll-out's graph."""
+        from .sensors import cast_rays
+        return cast_rays(self.geom, self.p, rays, **kw)
