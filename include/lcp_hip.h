@@ -718,6 +718,62 @@ int lcp_cast_rays_backward_f64(int B, int nb, int nvcap, int scene_verts_max, in
                                double* g_p, double* g_radius, double* g_verts_local, double* g_ray_origin, double* g_ray_angle,
                                void* stream);
 
+/* ---- proximity queries: the signed distance between body pairs, differentiable ----
+ * How far apart two bodies are - negative when they overlap - with the unit normal from the first towards the second and a witness
+ * point on either surface, for P pairs per scene and B scenes in one launch (lcp_proximity.hip).  Where the contact list has a record
+ * (within eps of touching) dist is minus the largest penetration of the pair's records; the query continues it to pairs that are
+ * apart.  The scene inputs, their limits and the world vertices w_i, edges e_i = w_i+1 - w_i and outward unit normals n_i are exactly
+ * those of lcp_render_f64 / lcp_cast_rays_f64.  no_contact is not consulted: a query is explicit.
+ *   pairs, P per scene: pair_first[B,P] i32 (body 1), pair_second[B,P] i32 (body 2), pair_max_dist[B,P] f64 > 0 (+inf allowed).
+ *   per pair: dist, n (unit, from body 1 towards body 2), w1 on body 1's surface, w2 on body 2's, world frame; dist = n . (w2 - w1).
+ *       circle - circle   q = c2 - c1, dist = |q| - r1 - r2, n = q / |q| (0 when |q| == 0), w1 = c1 + r1 n, w2 = c2 - r2 n.
+ *       circle 1 - hull 2 (d, edge, t, u) = the signed distance of hull 2 at c1 with its derivative data: outside, the nearest edge
+ *               (the smallest squared point-to-segment distance, the first on ties) with t clamped to [0, 1] and u = (c1 - foot) / d;
+ *               inside (max_i h_i <= 0, h_i = n_i . (c1 - w_i)) the edge of largest h_i, the first i on ties, u = n_i, d = h_i, t =
+ *               (c1 - w_i) . e_i / |e_i|^2 unclamped.  dist = d - r1, n = -u, w1 = c1 - r1 u, w2 = c1 - d u.
+ *       hull 1 - circle 2 the mirror image with n = u.
+ *       hull A (1) - hull B (2)   sep_A = max_i min_j n^A_i . (b_j - a_i), the first i on ties of the max and the first j on ties of
+ *               the min; sep_B likewise with the roles swapped.
+ *               max(sep_A, sep_B) <= 0 (overlapping or touching): dist is that maximum; A's face wins when sep_A >= sep_B.  A's face i
+ *                   with its support vertex b_j: n = n^A_i, w2 = b_j, w1 = b_j - dist n, t = (b_j - a_i) . e_i / |e_i|^2 (unclamped);
+ *                   B's face j with a_i: n = -n^B_j, w1 = a_i, w2 = a_i + dist n, t on B's edge.
+ *               otherwise (apart): dist is the smallest point-to-segment distance over two sets, in this order: every b_j against every
+ *                   edge i of A (i outer, j inner), then every a_i against every edge j of B (j outer, i inner); squared distances
+ *                   are compared and a strict < keeps the first on ties.  The witness on the edge's body is the foot point at the
+ *                   clamped t, the witness on the other body is the vertex, n = (w2 - w1) / dist.  dist > 0 here.
+ *   invalid: pair_first == pair_second, an index outside [0, nb), or a hull of fewer than three vertices: dist = max_dist.
+ *   clamp:   any dist >= max_dist is returned as max_dist with n = w1 = w2 = 0 and no gradient.
+ *   cull:    a pair whose bounding circles (the staged ones, which only over-estimate) are max_dist or more apart is not evaluated;
+ *            its true distance is at least max_dist too, so no result depends on the cull.
+ *   a scene with more hull vertices than scene_verts_max is not queried: every pair returns max_dist.
+ *   out (each optional, at least one; written, never accumulated): dist[B,P] f64, normal[B,P,2] f64, w1[B,P,2] f64, w2[B,P,2] f64.
+ * Sizes: those of lcp_cast_rays_f64 (1 <= nb <= 64, 8 <= nvcap <= 64, 0 <= scene_verts_max <= 1024), 1 <= P <= 1024, B >= 0; a NULL
+ * scene or pair array, no output - anything else is LCP_E_BADARG before any launch.  B == 0: success, no launch.  fp64 arithmetic.
+ * One workgroup per (scene, 256 pairs), lane = pair, the cull decided before the pair's loops.  No allocation, no synchronisation, no
+ * global state. */
+int lcp_pair_distance_f64(int B, int nb, int nvcap, int scene_verts_max, int P,
+                          const int32_t* kind, const double* radius, const double* verts_local, const int32_t* nverts,
+                          const double* p,
+                          const int32_t* pair_first, const int32_t* pair_second, const double* pair_max_dist,
+                          double* dist, double* normal, double* w1, double* w2, void* stream);
+
+/* Backward of dist of lcp_pair_distance_f64.  Same inputs and checks; nothing is saved by the forward, every pair is recomputed.
+ *   in: g_dist[B,P] f64 (required).
+ *   out (each optional, at least one; written, never accumulated): g_p[B,nb,3] f64, g_radius[B,nb] f64 (hulls: 0),
+ *       g_verts_local[B,nb,nvcap,2] f64 (body frame; circles and slots >= nverts: 0).
+ * A pair with dist < max_dist differentiates by
+ *       d(dist) = n . (dW2 - dW1) - dr1 - dr2
+ *   dW: the motion of the material witness point - a circle: dc; a hull's vertex: dw; a point of a hull's edge: (1 - t) dw_i + t dw_i+1
+ *       with dw = dc + drot perp(w - c) + R(rot) dv_local, perp(x, y) = (-y, x);  dr: a circle's radius (a hull: 0).
+ * Invalid, culled and clamped pairs have zero gradient.  One workgroup per scene, the pairs' terms staged in LDS behind the scene
+ * (48 bytes a pair), every body owned by one wavefront that sums over the pairs in order - no atomics, two runs give the same bits. */
+int lcp_pair_distance_backward_f64(int B, int nb, int nvcap, int scene_verts_max, int P,
+                                   const int32_t* kind, const double* radius, const double* verts_local, const int32_t* nverts,
+                                   const double* p,
+                                   const int32_t* pair_first, const int32_t* pair_second, const double* pair_max_dist,
+                                   const double* g_dist,
+                                   double* g_p, double* g_radius, double* g_verts_local, void* stream);
+
 /* ---- the breakout encoder: frames -> paddle, blocks and ball of every scene ----
  * What extract_params (experiments/breakout/encoder.py:63-133, with remove_rect :136-137 and get_pos_dims :140-145) reads off
  * an Atari Breakout frame, for B frames in one launch (lcp_encoder.hip).  The reference reads channel 0 only (`frame[..., 0]`):

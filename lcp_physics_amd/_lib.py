@@ -89,6 +89,9 @@ SIGNATURES = {
     # the range sensors: sizes, the scene, the rays (body, origin, angle, range), then the outputs
     "lcp_cast_rays_f64": (_I, [_I] * 5 + [_P] * 5 + [_P] * 4 + [_P] * 3 + [_P]),
     "lcp_cast_rays_backward_f64": (_I, [_I] * 5 + [_P] * 5 + [_P] * 4 + [_P] + [_P] * 5 + [_P]),
+    # the proximity queries: sizes, the scene, the pairs (first, second, max_dist), then the outputs
+    "lcp_pair_distance_f64": (_I, [_I] * 5 + [_P] * 5 + [_P] * 3 + [_P] * 4 + [_P]),
+    "lcp_pair_distance_backward_f64": (_I, [_I] * 5 + [_P] * 5 + [_P] * 3 + [_P] + [_P] * 3 + [_P]),
     "lcp_extract_params_u8": (_I, [_I] * 3 + [_P] + [_c.c_int64] * 3 + [_P, _I] + [_P] * 8 + [_P]),
     "lcp_joint_jacobian_backward_f64": (_I, [_I] * 4 + [_P] * 6 + [_P, _P, _P]),
     "lcp_state_update_backward_f64": (_I, [_I] * 3 + [_P] * 5 + [_c.c_double] + [_P] * 3 + [_P]),

@@ -844,6 +844,39 @@ int lcp_cast_rays_backward_f64(int B, int nb, int nvcap, int scene_verts_max, in
                                         ray_angle, ray_range, g_dist, g_p, g_radius, g_verts_local, g_ray_origin, g_ray_angle, stream);
 }
 
+// what both proximity entries refuse before any launch: a negative batch, sizes outside the packed vertex list's, a pair count
+// outside 1..1024, a missing scene or pair array
+static bool pair_distance_args_ok(int B, int nb, int nvcap, int scene_verts_max, int P, const void* kind, const void* radius,
+                                  const void* verts_local, const void* nverts, const void* p, const void* pair_first,
+                                  const void* pair_second, const void* pair_max_dist) {
+  if (B < 0 || !lcp::pair_distance_supported(nb, nvcap, scene_verts_max, P)) return false;
+  return kind && radius && verts_local && nverts && p && pair_first && pair_second && pair_max_dist;
+}
+
+int lcp_pair_distance_f64(int B, int nb, int nvcap, int scene_verts_max, int P, const int32_t* kind, const double* radius,
+                          const double* verts_local, const int32_t* nverts, const double* p, const int32_t* pair_first,
+                          const int32_t* pair_second, const double* pair_max_dist, double* dist, double* normal, double* w1, double* w2,
+                          void* stream) {
+  if (!pair_distance_args_ok(B, nb, nvcap, scene_verts_max, P, kind, radius, verts_local, nverts, p, pair_first, pair_second, pair_max_dist))
+    return LCP_E_BADARG;
+  if (!dist && !normal && !w1 && !w2) return LCP_E_BADARG;            // (nothing asked for)
+  if (B == 0) return 0;
+  return lcp::pair_distance_launch(B, nb, nvcap, scene_verts_max, P, kind, radius, verts_local, nverts, p, pair_first, pair_second,
+                                   pair_max_dist, dist, normal, w1, w2, stream);
+}
+
+int lcp_pair_distance_backward_f64(int B, int nb, int nvcap, int scene_verts_max, int P, const int32_t* kind, const double* radius,
+                                   const double* verts_local, const int32_t* nverts, const double* p, const int32_t* pair_first,
+                                   const int32_t* pair_second, const double* pair_max_dist, const double* g_dist, double* g_p,
+                                   double* g_radius, double* g_verts_local, void* stream) {
+  if (!pair_distance_args_ok(B, nb, nvcap, scene_verts_max, P, kind, radius, verts_local, nverts, p, pair_first, pair_second, pair_max_dist))
+    return LCP_E_BADARG;
+  if (!g_dist || (!g_p && !g_radius && !g_verts_local)) return LCP_E_BADARG;
+  if (B == 0) return 0;
+  return lcp::pair_distance_backward_launch(B, nb, nvcap, scene_verts_max, P, kind, radius, verts_local, nverts, p, pair_first,
+                                            pair_second, pair_max_dist, g_dist, g_p, g_radius, g_verts_local, stream);
+}
+
 // the layout words of lcp_extract_params_u8 against an H x W image (include/lcp_hip.h lists what is refused)
 static bool encoder_layout_ok(const int32_t* w, int H, int W) {
   const int paddle_line = w[0], paddle_h = w[1], paddle_w = w[2], paddle_key = w[3], ball_w = w[4], nrows = w[5], band_top = w[6],

@@ -300,6 +300,18 @@ int cast_rays_backward_launch(int B, int nb, int nvcap, int scene_verts_max, int
                               double* g_p, double* g_radius, double* g_verts_local, double* g_ray_origin, double* g_ray_angle,
                               void* stream);
 
+// lcp_proximity.hip: the signed distance between body pairs (include/lcp_hip.h, "proximity queries") and the backward of the
+// distances; arguments checked by the caller
+bool pair_distance_supported(int nb, int nvcap, int scene_verts_max, int P);      // render_supported and 1 <= P <= 1024
+int pair_distance_launch(int B, int nb, int nvcap, int scene_verts_max, int P, const int32_t* kind, const double* radius,
+                         const double* verts_local, const int32_t* nverts, const double* p, const int32_t* pair_first,
+                         const int32_t* pair_second, const double* pair_max_dist, double* dist, double* normal, double* w1, double* w2,
+                         void* stream);
+int pair_distance_backward_launch(int B, int nb, int nvcap, int scene_verts_max, int P, const int32_t* kind, const double* radius,
+                                  const double* verts_local, const int32_t* nverts, const double* p, const int32_t* pair_first,
+                                  const int32_t* pair_second, const double* pair_max_dist, const double* g_dist, double* g_p,
+                                  double* g_radius, double* g_verts_local, void* stream);
+
 // lcp_encoder.hip: the breakout encoder (experiments/breakout/encoder.py:63-145), one workgroup per frame; arguments checked by
 // the caller, `layout` the LCP_ENC_LAYOUT_WORDS host words
 int extract_params_launch(int B, int H, int W, const uint8_t* frame, long long stride_b, long long stride_row, long long stride_col,

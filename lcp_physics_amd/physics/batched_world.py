@@ -1038,3 +1038,10 @@ class ContactWorld:
         distances are part of the roll-out's graph."""
         from .sensors import cast_rays
         return cast_rays(self.geom, self.p, rays, **kw)
+
+    def clearance(self, pairs, **kw):
+        """The signed distance between the body pairs of every scene, `dist [B,P]` f64 (`physics.proximity.pair_distances(self.geom,
+        self.p, pairs, **kw)`; `witnesses=True` adds the normal and the two witness points), at the pose `render` draws.  After
+        `step(differentiable=True)` the distances are part of the roll-out's graph."""
+        from .proximity import pair_distances
+        return pair_distances(self.geom, self.p, pairs, **kw)
