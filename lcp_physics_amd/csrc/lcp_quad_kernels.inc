@@ -42,6 +42,9 @@
 #ifndef LCP_Q_FORM_BLOCKS_BWD
 #define LCP_Q_FORM_BLOCKS_BWD 0   // the same in bwd_solve_body (one formation per launch, the weights of a group read from LDS when its first block is met).  Measured and OFF: dense backward 23.75 / 23.84 us without, 23.89 / 23.91 us with it (profiles/r11_ab_form_blocks.txt) - the kernel is bound by its stores
 #endif
+#ifndef LCP_Q_MASK_LOCAL
+#define LCP_Q_MASK_LOCAL 1    // sized pinned forward with register columns: solve_kkt_pq forms its lane masks per call (0: once per kernel, spilled; A/B)
+#endif
 #ifndef LCP_Q_BEST_LDS
 #define LCP_Q_BEST_LDS 1      // 0: the pinned body-space kernel keeps its best iterate in registers (A/B aid)
 #endif
@@ -103,7 +106,9 @@ template <int C0> __device__ __forceinline__ void gtw8_dpp(double& a0, double& a
       LCP_GTW_ONE(a0, wn, g2, k2) LCP_GTW_ONE(a1, wt, t2_, k2) LCP_GTW_ONE(a2, wn, g3, k3) LCP_GTW_ONE(a3, wt, t3_, k3)
       LCP_GTW_ONE(a0, wn, g4, k4) LCP_GTW_ONE(a1, wt, t4_, k4) LCP_GTW_ONE(a2, wn, g5, k5) LCP_GTW_ONE(a3, wt, t5_, k5)
       LCP_GTW_ONE(a0, wn, g6, k6) LCP_GTW_ONE(a1, wt, t6_, k6) LCP_GTW_ONE(a2, wn, g7, k7) LCP_GTW_ONE(a3, wt, t7_, k7)
-      : [a0] "+v"(a0), [a1] "+v"(a1), [a2] "+v"(a2), [a3] "+v"(a3)
+      // (early-clobber: where wn / wt and the accumulators all start as the constant zero - the post-stabilisation forms - the register
+      //  allocator otherwise gives an accumulator the register of its own DPP source; tools/isa_lint.py --dpp-all found it)
+      : [a0] "+&v"(a0), [a1] "+&v"(a1), [a2] "+&v"(a2), [a3] "+&v"(a3)
       : [wn] "v"(wn), [wt] "v"(wt), [g0] "v"(g[0]), [g1] "v"(g[1]), [g2] "v"(g[2]), [g3] "v"(g[3]), [g4] "v"(g[4]), [g5] "v"(g[5]), [g6] "v"(g[6]), [g7] "v"(g[7]),
         [t0_] "v"(t[0]), [t1_] "v"(t[1]), [t2_] "v"(t[2]), [t3_] "v"(t[3]), [t4_] "v"(t[4]), [t5_] "v"(t[5]), [t6_] "v"(t[6]), [t7_] "v"(t[7]),
         [k0] "n"(C0), [k1] "n"(C0 + 1), [k2] "n"(C0 + 2), [k3] "n"(C0 + 3), [k4] "n"(C0 + 4), [k5] "n"(C0 + 5), [k6] "n"(C0 + 6), [k7] "n"(C0 + 7));
@@ -601,6 +606,25 @@ __device__ __forceinline__ bool factor_pq(TC (&xr)[20], TC (&er)[20], PQ& R, con
   LCP_QTICK(pr, 1)                                                               // formation
   bool singular = false;
   R.udx = 1; R.ude = 1;
+  // LCP_Q_LU_AHEAD (sized pinned forward with register columns, fp64): a step is one statement that carries the next pivot's reciprocal
+  // inside its column block - lcp_quad_prims.h, lu_step_x - and stops at column CHI-1 (the blocks of the form below go on to column 15, which
+  // nothing reads when nz < 16).
+  constexpr bool LUAH = (LCP_Q_LU_AHEAD != 0) && PQ::TRIM_ && SQ::COLR_ && std::is_same<TC, double>::value;
+  if constexpr (LUAH) {
+    TC pivv = bc<CLO>(xr[CLO]);
+    TC inv = fast_rcp(pivv);
+    static_for<CHI - CLO>([&](auto Kq) LCP_INL {
+      constexpr int k = CLO + Kq;
+      singular = singular || (pivv == (TC)0);
+      const TC sk = xr[k] * inv;                                                       // (as below: column k scaled on every row but k)
+      const TC lx = keep_if(sk, l16 > k);
+      xr[k] = (l16 == k) ? xr[k] : sk;
+      R.udx = (l16 == k) ? inv : R.udx;
+      if constexpr (k + 1 < CHI) lu_step_x<k, CHI - k - 2>(xr, lx, pivv, inv);
+    });
+    LCP_QTICK(pr, 2)                                                             // LU
+    return singular;
+  } else
   if (R.pin()) {
     // x pivots e .. nz-1 only, one row per lane, columns k+1 .. 15
     TC pivv = bc<0>(xr[0]);                                                      // (placeholder until the first live step)
@@ -670,7 +694,9 @@ template <typename TI, typename TC, typename PQ, typename SQ>
 __device__ __forceinline__ void solve_kkt_pq(const SQ& S, const TC (&xr)[20], const TC (&er)[20], const PQ& R,
                                              const M4<TC>& di, bool valid, const XV<TC, 1>& rx, const M4<TC>& rs, const M4<TC>& rz, TC ry,
                                              XV<TC, 1>& ox, M4<TC>& os, M4<TC>& oz, TC& oy LCP_QPROF_ARG) {
-  const int l16 = S.l16;
+  // (LCP_Q_MASK_LOCAL: the lane masks `l16 > k` / `l16 < k` of the sweeps formed here, per solve, instead of once per kernel - hoisted they
+  //  overflow the SGPR file and every use reloads one through two v_readlane; as in factor_pq)
+  const int l16 = (LCP_Q_MASK_LOCAL != 0 && PQ::TRIM_ && SQ::COLR_) ? launder(S.l16) : S.l16;
   const int nz = PQ::NZF_ > 0 ? PQ::NZF_ : __builtin_amdgcn_readfirstlane(S.nz), e = PQ::NZF_ > 0 ? PQ::EF_ : __builtin_amdgcn_readfirstlane(S.e);
   M4<TC> q = m4<TC>(rs.n * di.n - rz.n, rs.f1 * di.f1 - rz.f1, rs.f2 * di.f2 - rz.f2, rs.g * di.g - rz.g);
   if (!valid) q = m4<TC>(0, 0, 0, 0);

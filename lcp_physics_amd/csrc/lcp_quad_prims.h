@@ -188,8 +188,10 @@ template <typename TC> __device__ __forceinline__ TC sum4(const M4<TC>& a) { ret
 // skips FMAC), so it is emitted as inline asm - and inline asm is invisible to the hazard recogniser: gfx950 needs 2 wait
 // states between a VALU write of a VGPR and a DPP read of it (tools/microbench/dpp_hazard.hip shows stale reads
 // without them).  Every asm statement below therefore starts with `s_nop 1` (covers whatever the compiler put in front:
-// copies, v_accvgpr_read ...) and inside a statement no DPP source is written before it is read; up to 14 column pairs
-// (30 operands) share one s_nop.
+// copies, v_accvgpr_read ...) and inside a statement a DPP source that the statement wrote is read two issue slots later at
+// the earliest (only lu_step_x writes one at all); up to 14 column pairs (30 operands) share one s_nop.  The same holds for
+// the one other hazard such a statement can meet, a transcendental result (v_rcp_f64) read by the next VALU instruction: one
+// slot between them.  tools/isa_lint.py --dpp-all (`make lint`) checks both rules on the assembled library.
 #define LCP_DPP_FULL "row_mask:0xf bank_mask:0xf"
 #define LCP_LUA_COL(A, U)                                                                   \
   "v_fmac_f64_dpp %[" #U "], %[" #A "], -%[lu] row_newbcast:%[k] " LCP_DPP_FULL "\n\t"      \
@@ -345,6 +347,66 @@ template <int K, int J0, int N> __device__ __forceinline__ void lu_cols_x(double
 }
 template <int K, int J0, int N> __device__ __forceinline__ void lu_cols_x(float (&xr)[20], float lx) {
   static_for<N>([&](auto JJ) LCP_INL { constexpr int j = J0 + JJ; xr[j] = fmaf(-lx, bc<K>(xr[j]), xr[j]); });
+}
+// LCP_Q_LU_AHEAD: one whole step of the pinned LU as ONE statement, so that the look-ahead holds by construction.  Left to the scheduler,
+// the chain `next pivot's broadcast -> v_rcp_f64 -> two Newton steps` was placed BEHIND the column block it was written in front of, and
+// every pivot waited out six dependent instructions with nothing to issue between them.  The statement updates column K+1 first, puts two
+// column updates (or the wait states they stand for) between that write and the broadcast that reads it through DPP, and spreads the
+// reciprocal's chain over the remaining columns K+2 .. K+1+N.  Same instructions on the same accumulators as fnmac_bc + bc + fast_rcp +
+// lu_cols_x: bit for bit the same factors.  `pivv` / `inv` leave as the next step's pivot and its reciprocal.
+#ifndef LCP_Q_LU_AHEAD
+#define LCP_Q_LU_AHEAD 1    // 0: the earlier form (builtin update of column K+1, fast_rcp in C++, lu_cols_x behind them; A/B)
+#endif
+#define LCP_LUS_X1 "v_fmac_f64_dpp %[x1], %[x1], -%[lx] row_newbcast:%[k] " LCP_DPP_FULL "\n\t"
+#define LCP_LUS_C(I) "v_fmac_f64_dpp %[c" #I "], %[c" #I "], -%[lx] row_newbcast:%[k] " LCP_DPP_FULL "\n\t"
+#define LCP_LUS_P "v_mov_b64_dpp %[pv], %[x1] row_newbcast:%[k1] " LCP_DPP_FULL " bound_ctrl:1\n\t"
+#define LCP_LUS_R "v_rcp_f64_e32 %[r], %[pv]\n\t"
+#define LCP_LUS_FA "v_fma_f64 %[e], -%[pv], %[r], 1.0\n\t"
+#define LCP_LUS_FB "v_fmac_f64_e32 %[r], %[e], %[r]\n\t"
+// (v_rcp_f64 is a transcendental instruction: gfx950 needs one wait state before another VALU instruction reads its result, and inline
+//  asm gets none from the compiler - a column update, or `s_nop 0` where none is left, always stands between LCP_LUS_R and LCP_LUS_FA.
+//  N < 3: `s_nop` also stands in for the column updates that would separate the write of column K+1 from its DPP read.)
+#define LCP_LUS_NEWTON LCP_LUS_FA LCP_LUS_FB LCP_LUS_FA LCP_LUS_FB
+#define LCP_LUS_B0 LCP_LUS_X1 "s_nop 1\n\t" LCP_LUS_P LCP_LUS_R "s_nop 0\n\t" LCP_LUS_NEWTON
+#define LCP_LUS_B1 LCP_LUS_X1 "s_nop 1\n\t" LCP_LUS_P LCP_LUS_R LCP_LUS_C(0) LCP_LUS_NEWTON
+#define LCP_LUS_B2 LCP_LUS_X1 LCP_LUS_C(0) "s_nop 0\n\t" LCP_LUS_P LCP_LUS_R LCP_LUS_C(1) LCP_LUS_NEWTON
+#define LCP_LUS_H2 LCP_LUS_X1 LCP_LUS_C(0) LCP_LUS_C(1) LCP_LUS_P LCP_LUS_R
+#define LCP_LUS_B3 LCP_LUS_H2 LCP_LUS_C(2) LCP_LUS_NEWTON
+#define LCP_LUS_B4 LCP_LUS_H2 LCP_LUS_C(2) LCP_LUS_C(3) LCP_LUS_NEWTON
+#define LCP_LUS_B5 LCP_LUS_H2 LCP_LUS_C(2) LCP_LUS_C(3) LCP_LUS_FA LCP_LUS_C(4) LCP_LUS_FB LCP_LUS_FA LCP_LUS_FB
+#define LCP_LUS_B6 LCP_LUS_H2 LCP_LUS_C(2) LCP_LUS_C(3) LCP_LUS_FA LCP_LUS_C(4) LCP_LUS_FB LCP_LUS_C(5) LCP_LUS_FA LCP_LUS_FB
+#define LCP_LUS_B7 LCP_LUS_H2 LCP_LUS_C(2) LCP_LUS_C(3) LCP_LUS_FA LCP_LUS_C(4) LCP_LUS_FB LCP_LUS_C(5) LCP_LUS_FA LCP_LUS_C(6) LCP_LUS_FB
+#define LCP_LUS_B8 LCP_LUS_B7 LCP_LUS_C(7)
+#define LCP_LUS_B9 LCP_LUS_B8 LCP_LUS_C(8)
+#define LCP_LUS_B10 LCP_LUS_B9 LCP_LUS_C(9)
+#define LCP_LUS_B11 LCP_LUS_B10 LCP_LUS_C(10)
+#define LCP_LUS_B12 LCP_LUS_B11 LCP_LUS_C(11)
+#define LCP_LUS_O0 [x1] "+v"(xr[K + 1]), [pv] "=&v"(pivv), [r] "=&v"(inv), [e] "=&v"(e)
+#define LCP_LUS_O1 LCP_LUS_O0, [c0] "+v"(xr[K + 2])
+#define LCP_LUS_O2 LCP_LUS_O1, [c1] "+v"(xr[K + 3])
+#define LCP_LUS_O3 LCP_LUS_O2, [c2] "+v"(xr[K + 4])
+#define LCP_LUS_O4 LCP_LUS_O3, [c3] "+v"(xr[K + 5])
+#define LCP_LUS_O5 LCP_LUS_O4, [c4] "+v"(xr[K + 6])
+#define LCP_LUS_O6 LCP_LUS_O5, [c5] "+v"(xr[K + 7])
+#define LCP_LUS_O7 LCP_LUS_O6, [c6] "+v"(xr[K + 8])
+#define LCP_LUS_O8 LCP_LUS_O7, [c7] "+v"(xr[K + 9])
+#define LCP_LUS_O9 LCP_LUS_O8, [c8] "+v"(xr[K + 10])
+#define LCP_LUS_O10 LCP_LUS_O9, [c9] "+v"(xr[K + 11])
+#define LCP_LUS_O11 LCP_LUS_O10, [c10] "+v"(xr[K + 12])
+#define LCP_LUS_O12 LCP_LUS_O11, [c11] "+v"(xr[K + 13])
+template <int K, int N> struct LuStepX;              // pivot row K: column K+1, the next pivot and its reciprocal, columns K+2 .. K+1+N
+#define LCP_LUS_DEF(N)                                                                                                   \
+  template <int K> struct LuStepX<K, N> {                                                                                \
+    static __device__ __forceinline__ void run(double (&xr)[20], double lx, double& pivv, double& inv) {                 \
+      double e;                                                                                                          \
+      asm("s_nop 1\n\t" LCP_LUS_B##N : LCP_LUS_O##N : [lx] "v"(lx), [k] "n"(K), [k1] "n"(K + 1));                        \
+    }                                                                                                                    \
+  };
+LCP_LUS_DEF(0) LCP_LUS_DEF(1) LCP_LUS_DEF(2) LCP_LUS_DEF(3) LCP_LUS_DEF(4) LCP_LUS_DEF(5) LCP_LUS_DEF(6)
+LCP_LUS_DEF(7) LCP_LUS_DEF(8) LCP_LUS_DEF(9) LCP_LUS_DEF(10) LCP_LUS_DEF(11) LCP_LUS_DEF(12)
+template <int K, int N> __device__ __forceinline__ void lu_step_x(double (&xr)[20], double lx, double& pivv, double& inv) {
+  static_assert(LCP_FAST_RCP_STEPS == 2 && N >= 0 && K + 1 + N < 16, "two Newton steps, as fast_rcp; columns of one DPP row");
+  LuStepX<K, N>::run(xr, lx, pivv, inv);
 }
 // formation: xr[j] += a * (lane K's p0[j]) + b * (lane K's p1[j]) for eight columns
 // (the eight p0 terms first, then the eight p1 terms: the two updates of a column are eight instructions apart)

@@ -11,6 +11,8 @@ like, so this tool walks every kernel of a .s file, builds its control-flow grap
     (s_and_saveexec depth by linear scan - a heuristic: lanes that were off at the write hold whatever was there before).
 
 usage: tools/isa_lint.py file.s [--kernel SUBSTR] [--exec] [--max N]
+       tools/isa_lint.py --shadow-all DIR [--fixed]      vector instructions in the shadow of an exec restore (exec_shadow)
+       tools/isa_lint.py --dpp-all DIR [--fixed]         DPP / transcendental reads inside the wait states of the write (dpp_hazard)
 """
 import re
 import sys
@@ -135,16 +137,14 @@ def kernels_of(lines):
     return out
 
 
-def lint(lines, name, lo, hi, exec_mode=False, maxrep=40):
-    # blocks
+def blocks_of(lines, lo, hi):
+    """Basic blocks of one function body (lists of Ins, split at the .LBB labels and behind every branch) with their successors and predecessors"""
     blocks, label_of, cur = [], {}, []
     def close():
         nonlocal cur
         if cur:
             blocks.append(cur); cur = []
-    depth, depth_at = 0, {}
     pending_labels = []
-    block_labels = {}
     for i in range(lo + 1, hi):
         l = lines[i]
         m = re.match(r"^(\.LBB\d+_\d+):", l)
@@ -157,11 +157,6 @@ def lint(lines, name, lo, hi, exec_mode=False, maxrep=40):
             for lb in pending_labels:
                 label_of[lb] = len(blocks)
             pending_labels = []
-        if re.match(r"s_(and|or|xor|andn2)_saveexec_b64", ins.op):
-            depth += 1
-        elif re.match(r"s_or_b64 exec, exec,", ins.text) and depth > 0:
-            depth -= 1
-        depth_at[ins.line] = depth
         cur.append(ins)
         if ins.op.startswith(("s_branch", "s_cbranch", "s_endpgm")):
             close()
@@ -184,6 +179,12 @@ def lint(lines, name, lo, hi, exec_mode=False, maxrep=40):
     for b in range(nb):
         for s in succ[b]:
             pred[s].append(b)
+    return blocks, succ, pred
+
+
+def lint(lines, name, lo, hi, exec_mode=False, maxrep=40):
+    blocks, succ, pred = blocks_of(lines, lo, hi)
+    nb = len(blocks)
     # entry state: kernarg pointer, workgroup id, workitem id, exec, vcc (reserved)
     entry = {("s", k) for k in range(0, 16)} | {("v", 0), ("exec", 0)}
     ALL = None
@@ -313,6 +314,87 @@ def exec_shadow(lines, name, lo, hi, quiet=None):
     return sum(len(f[2]) for f in finds)
 
 
+DPP_CTRL = re.compile(r"\b(quad_perm:|row_(shl|shr|ror|bcast|newbcast|share|xmask|mirror|half_mirror)\b|wave_(shl|shr|rol|ror)\b|dpp8:)")
+DPP_WAIT = 2                         # issue slots gfx950 needs between a VALU write of a VGPR and a DPP read of it (tools/microbench/dpp_hazard.hip)
+
+
+def slots_of(ins):
+    """issue slots (wait states) an instruction fills: `s_nop N` stands for N + 1"""
+    if ins.op == "s_nop":
+        return int(ins.text.split()[1], 0) + 1
+    return 1
+
+
+def dpp_source(ins):
+    """the VGPRs an instruction reads THROUGH its DPP control (src0 only: the other sources and the accumulator are plain reads, no hazard)"""
+    if not (DPP_CTRL.search(ins.text) or "_dpp" in ins.op):
+        return []
+    ops = ins.text.split(None, 1)[1].split(",")
+    return [r for r in regs_of(ops[1]) if r[0] == "v"] if len(ops) > 1 else []
+
+
+TRANS_OPS = ("v_rcp_", "v_rsq_", "v_sqrt_", "v_exp_", "v_log_", "v_sin_", "v_cos_")
+TRANS_WAIT = 1                       # ... and between a transcendental instruction's write and a read of it by any other VALU instruction
+WAIT = {"dpp": DPP_WAIT, "trans": TRANS_WAIT}
+
+
+def dpp_hazard(lines, name, lo, hi, quiet=None):
+    """The two gfx950 wait-state rules that hand-written statements must keep themselves: no DPP read of a VGPR that a VALU instruction
+    wrote in the DPP_WAIT preceding issue slots ("dpp"), and no VALU read of a transcendental instruction's result in the slot behind it
+    ("trans").  The compiler's hazard recogniser pads its own code; inline asm is invisible to it, and the v_fmac_f64_dpp statements of
+    lcp_quad_prims.h are safe by their own rules (`s_nop 1` first, DPP sources written two slots ahead, a slot behind v_rcp_f64) - this
+    check holds the assembled code to them.  Per basic block; at a block's entry the last slots of every predecessor count (fixed point
+    over the control-flow graph).  A finding: (line, register, instruction, slots between, rule)."""
+    blocks, succ, pred = blocks_of(lines, lo, hi)
+    nb = len(blocks)
+
+    def walk(b, state, finds):
+        age = dict(state)                                # (rule, VGPR) -> issue slots between its write and the next instruction
+        for ins in blocks[b]:
+            valu, trans = ins.op.startswith("v_"), ins.op.startswith(TRANS_OPS)
+            if finds is not None:
+                for r in dpp_source(ins):
+                    if ("dpp", r) in age:
+                        finds.append((ins.line, "v%d" % r[1], ins.text, age[("dpp", r)], "dpp"))
+                for r in (ins.uses if valu and not trans else []):
+                    if ("trans", r) in age:
+                        finds.append((ins.line, "v%d" % r[1], ins.text, age[("trans", r)], "trans"))
+            n = slots_of(ins)
+            age = {k: d + n for k, d in age.items() if d + n < WAIT[k[0]]}
+            if valu:
+                wrote = [r for r in ins.defs if r[0] == "v"] + ([ins.lane_def[0]] if ins.lane_def else [])
+                for r in wrote:
+                    age[("dpp", r)] = 0
+                    if trans:
+                        age[("trans", r)] = 0
+        return age
+
+    IN = [dict() for _ in range(nb)]
+    OUT = [None] * nb
+    work = list(range(nb))
+    while work:
+        b = work.pop(0)
+        inn = {}
+        for p in pred[b]:
+            for r, d in (OUT[p] or {}).items():
+                inn[r] = min(d, inn.get(r, d))
+        out = walk(b, inn, None)
+        if OUT[b] is None or out != OUT[b] or inn != IN[b]:
+            IN[b], OUT[b] = inn, out
+            work += [s for s in succ[b] if s not in work]
+    finds = []
+    for b in range(nb):
+        walk(b, IN[b], finds)
+    if quiet is not None:
+        quiet.extend(finds)
+        return len(finds)
+    if finds or "--verbose" in sys.argv:
+        print("== %s: %d reads inside the wait states of a VALU write" % (name[:110], len(finds)))
+    for ln, reg, t, d, rule in finds[:20]:
+        print("   line %6d  %-5s %-6s written %d slot(s) before  %s" % (ln, rule, reg, d + 1, t))
+    return len(finds)
+
+
 SPILL_OPS = ("v_accvgpr_write_b32", "v_accvgpr_read_b32", "scratch_store_dword", "scratch_load_dword")
 
 
@@ -388,6 +470,21 @@ def main():
                 n = exec_shadow(lines, os.path.basename(f) + ":" + name, lo, hi)
                 total += n
         print("isa_lint --shadow-all: %d kernels, %d vector instructions in the shadow of an exec restore" % (nk, total))
+        sys.exit(1 if total else 0)
+    if "--dpp-all" in args:                          # the DPP wait-state check over every .s of a directory; exit status 1 on a finding
+        import glob
+        import os
+        d = args[args.index("--dpp-all") + 1]
+        total, nk = 0, 0
+        fixed_only = "--fixed" in args
+        for f in sorted(glob.glob(os.path.join(d, "*.s"))):
+            if fixed_only != f.endswith(".fixed.s"):
+                continue
+            lines = open(f).read().split("\n")
+            for name, lo, hi in kernels_of(lines):
+                nk += 1
+                total += dpp_hazard(lines, os.path.basename(f) + ":" + name, lo, hi)
+        print("isa_lint --dpp-all: %d kernels, %d DPP / transcendental reads inside the wait states of the write" % (nk, total))
         sys.exit(1 if total else 0)
     if "--shadow" in args:
         lines = open(args[0]).read().split("\n")
