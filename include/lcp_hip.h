@@ -774,6 +774,51 @@ int lcp_pair_distance_backward_f64(int B, int nb, int nvcap, int scene_verts_max
                                    const double* g_dist,
                                    double* g_p, double* g_radius, double* g_verts_local, void* stream);
 
+/* ---- force elements: springs, motors and drag as a function of the state, differentiable ----
+ * Forces that depend on the state of the scene - a spring or damper between two anchors, a PD servo on a relative angle, viscous
+ * drag - for E elements per scene and B scenes in one launch (lcp_forces.hip), added onto an optional base force.
+ *   state:   p[B,nb,3] f64 (rot, x, y); v[B,nb,3] f32 (w, vx, vy).  A wrench is (torque, fx, fy), the order of p and v.
+ *            cross(a, b) = ax by - ay bx, perp(x, y) = (-y, x), R(rot) = [[cos, -sin], [sin, cos]] (utils.py:105-112).
+ *   elements, [B,E] each (scenes may differ in every array): kind i32 (0 none, 1 spring, 2 motor, 3 drag), b1, b2 i32,
+ *            a1, a2 [B,E,2] f64 (anchors), k, c, x0, w0, limit f64 (limit > 0, +inf allowed).
+ *   spring / damper (1): either body may be -1, the world: its anchor is then in world coordinates and at rest.
+ *            r_i = R(rot_i) a_i, P_i = c_i + r_i, V_i = (vx, vy)_i + w_i perp(r_i)       (the world: P_i = a_i, V_i = 0)
+ *            d = P_2 - P_1, L = |d|, u = d / L, Ldot = u . (V_2 - V_1)
+ *            s = k (L - x0) + c Ldot, clamped to [-limit, limit]
+ *            body 1 receives (cross(r_1, s u), s u), body 2 (cross(r_2, -s u), -s u).  L == 0: no force, zero gradient.
+ *   motor (2): a PD servo on the relative angle; b1 is the base, b2 the driven body; either may be -1 (the world: angle 0, at rest).
+ *            th = rot_2 - rot_1 (no wrapping: rot accumulates), om = w_2 - w_1
+ *            tau = k (x0 - th) + c (w0 - om), clamped to [-limit, limit]; +tau on b2's rotation, -tau on b1's.
+ *   drag (3): body b1 receives (-c w, -k vx, -k vy); b2, the anchors, x0, w0 and limit are ignored (b2 is not even checked).
+ *   invalid: kind 0 or unknown; spring or motor with an index outside [-1, nb) or b1 == b2 (which covers both ends the world);
+ *            drag with b1 outside [0, nb).  An invalid element produces nothing and has zero gradient.
+ *   a saturated element (|s| or |tau| >= limit) acts with +-limit and has zero gradient with respect to everything; limit has none.
+ *   out: f_out[B,nb,3] f32 = f_base + the sum of the elements' wrenches on the body.  f_base[B,nb,3] f32 is optional (NULL: 0) and
+ *            f_out may alias it.  Every entry is accumulated in fp64, starting from f_base, over the elements IN ELEMENT ORDER and
+ *            rounded once at the store; a body that no element touches gets f_base's bits.
+ * Sizes: 1 <= nb <= 64, 1 <= E <= 1024, B >= 0; a NULL element array, p, v or f_out - anything else is LCP_E_BADARG before any
+ * launch.  B == 0: success, no launch.  A group of lanes per scene (the power of two >= max(nb, E), at most 256; several scenes share
+ * a wavefront below 64), the elements' wrenches staged in LDS (40 bytes an element), every body's sum owned by one lane: no atomics,
+ * two runs give the same bits.  No allocation, no synchronisation, no global state. */
+int lcp_force_elements_f64(int B, int nb, int E,
+                           const int32_t* kind, const int32_t* b1, const int32_t* b2, const double* a1, const double* a2,
+                           const double* k, const double* c, const double* x0, const double* w0, const double* limit,
+                           const double* p, const float* v, const float* f_base, float* f_out, void* stream);
+
+/* Backward of lcp_force_elements_f64.  Same inputs and checks; nothing is saved by the forward, every element is evaluated again.
+ *   in: g_f[B,nb,3] f32 (required), the cotangent of f_out.  (The cotangent of f_base is g_f itself.)
+ *   out (each optional, at least one; written everywhere, never accumulated; all f64): g_p[B,nb,3], g_v[B,nb,3], g_k, g_c, g_x0,
+ *       g_w0 [B,E], g_a1, g_a2 [B,E,2].  Invalid and saturated elements and springs with L == 0: exactly 0.  A world-anchored end's
+ *       g_a is the gradient of its world point.  A drag's k is its linear and c its angular coefficient.
+ * Every body's sums are owned by one lane that walks the elements in order (staged 512 at a time, 72 bytes an element): no atomics,
+ * two runs give the same bits, whichever outputs are asked for. */
+int lcp_force_elements_backward_f64(int B, int nb, int E,
+                                    const int32_t* kind, const int32_t* b1, const int32_t* b2, const double* a1, const double* a2,
+                                    const double* k, const double* c, const double* x0, const double* w0, const double* limit,
+                                    const double* p, const float* v, const float* g_f,
+                                    double* g_p, double* g_v, double* g_k, double* g_c, double* g_x0, double* g_w0,
+                                    double* g_a1, double* g_a2, void* stream);
+
 /* ---- the breakout encoder: frames -> paddle, blocks and ball of every scene ----
  * What extract_params (experiments/breakout/encoder.py:63-133, with remove_rect :136-137 and get_pos_dims :140-145) reads off
  * an Atari Breakout frame, for B frames in one launch (lcp_encoder.hip).  The reference reads channel 0 only (`frame[..., 0]`):

@@ -877,6 +877,33 @@ int lcp_pair_distance_backward_f64(int B, int nb, int nvcap, int scene_verts_max
                                             pair_second, pair_max_dist, g_dist, g_p, g_radius, g_verts_local, stream);
 }
 
+// what both force-element entries refuse before any launch: a negative batch, sizes outside the limits, a missing element or state array
+static bool force_elements_args_ok(int B, int nb, int E, const void* kind, const void* b1, const void* b2, const void* a1, const void* a2,
+                                   const void* k, const void* c, const void* x0, const void* w0, const void* limit, const void* p,
+                                   const void* v) {
+  if (B < 0 || !lcp::force_elements_supported(nb, E)) return false;
+  return kind && b1 && b2 && a1 && a2 && k && c && x0 && w0 && limit && p && v;
+}
+
+int lcp_force_elements_f64(int B, int nb, int E, const int32_t* kind, const int32_t* b1, const int32_t* b2, const double* a1,
+                           const double* a2, const double* k, const double* c, const double* x0, const double* w0, const double* limit,
+                           const double* p, const float* v, const float* f_base, float* f_out, void* stream) {
+  if (!force_elements_args_ok(B, nb, E, kind, b1, b2, a1, a2, k, c, x0, w0, limit, p, v) || !f_out) return LCP_E_BADARG;
+  if (B == 0) return 0;
+  return lcp::force_elements_launch(B, nb, E, kind, b1, b2, a1, a2, k, c, x0, w0, limit, p, v, f_base, f_out, stream);
+}
+
+int lcp_force_elements_backward_f64(int B, int nb, int E, const int32_t* kind, const int32_t* b1, const int32_t* b2, const double* a1,
+                                    const double* a2, const double* k, const double* c, const double* x0, const double* w0,
+                                    const double* limit, const double* p, const float* v, const float* g_f, double* g_p, double* g_v,
+                                    double* g_k, double* g_c, double* g_x0, double* g_w0, double* g_a1, double* g_a2, void* stream) {
+  if (!force_elements_args_ok(B, nb, E, kind, b1, b2, a1, a2, k, c, x0, w0, limit, p, v)) return LCP_E_BADARG;
+  if (!g_f || (!g_p && !g_v && !g_k && !g_c && !g_x0 && !g_w0 && !g_a1 && !g_a2)) return LCP_E_BADARG;
+  if (B == 0) return 0;
+  return lcp::force_elements_backward_launch(B, nb, E, kind, b1, b2, a1, a2, k, c, x0, w0, limit, p, v, g_f, g_p, g_v, g_k, g_c, g_x0,
+                                             g_w0, g_a1, g_a2, stream);
+}
+
 // the layout words of lcp_extract_params_u8 against an H x W image (include/lcp_hip.h lists what is refused)
 static bool encoder_layout_ok(const int32_t* w, int H, int W) {
   const int paddle_line = w[0], paddle_h = w[1], paddle_w = w[2], paddle_key = w[3], ball_w = w[4], nrows = w[5], band_top = w[6],

@@ -312,6 +312,16 @@ int pair_distance_backward_launch(int B, int nb, int nvcap, int scene_verts_max,
                                   const int32_t* pair_second, const double* pair_max_dist, const double* g_dist, double* g_p,
                                   double* g_radius, double* g_verts_local, void* stream);
 
+// lcp_forces.hip: the force elements (include/lcp_hip.h, "force elements") and their backward; arguments checked by the caller
+bool force_elements_supported(int nb, int E);                                     // 1 <= nb <= 64 and 1 <= E <= 1024
+int force_elements_launch(int B, int nb, int E, const int32_t* kind, const int32_t* b1, const int32_t* b2, const double* a1,
+                          const double* a2, const double* k, const double* c, const double* x0, const double* w0, const double* limit,
+                          const double* p, const float* v, const float* f_base, float* f_out, void* stream);
+int force_elements_backward_launch(int B, int nb, int E, const int32_t* kind, const int32_t* b1, const int32_t* b2, const double* a1,
+                                   const double* a2, const double* k, const double* c, const double* x0, const double* w0,
+                                   const double* limit, const double* p, const float* v, const float* g_f, double* g_p, double* g_v,
+                                   double* g_k, double* g_c, double* g_x0, double* g_w0, double* g_a1, double* g_a2, void* stream);
+
 // lcp_encoder.hip: the breakout encoder (experiments/breakout/encoder.py:63-145), one workgroup per frame; arguments checked by
 // the caller, `layout` the LCP_ENC_LAYOUT_WORDS host words
 int extract_params_launch(int B, int H, int W, const uint8_t* frame, long long stride_b, long long stride_row, long long stride_col,

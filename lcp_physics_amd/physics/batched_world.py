@@ -632,11 +632,18 @@ class ContactWorld:
     step: `lcp_post_stabilization_f32` (frictionless LCP + correction move) and a contact re-detection.
     `broadphase=True` (off by default) runs every detection on `lcp_move_find_contacts_bp_f64` (lcp_contacts_bp.hip): the body pairs are
     culled by bounding circle and box before the narrow phase, the records are the same bit for bit, `candidates` [B] counts the survivors.
+    `elements=ForceSet` (physics/force_elements.py) adds forces that depend on the state - springs / dampers between anchors, PD motors
+    on a relative angle, viscous drag - onto `f` / `force_fn(t)`: one launch of `lcp_force_elements_f64` per step at the step's STARTING
+    `p` and `v` (evaluated once per `step_dt` and held through its dt halvings, as the reference evaluates `apply_forces(t)` once in
+    `solve_dynamics`; `fixed_dt=True` evaluates again in every sub-step), differentiable to `p`, `v`, `f` and the elements' parameters in
+    `step(differentiable=True)`.  The coupling is explicit: a spring of stiffness k on a mass m is stable only while
+    `dt sqrt(k / m) < 2` (a damper c: `dt c / m < 2`) - stiffer elements need a smaller `dt`; nothing here integrates them implicitly.
     """
 
     def __init__(self, geom, p, v, Mdiag, f, rest, fric, Je=None, dt=1.0 / 30, eps=0.1, tol=1e-6,
                  strict_no_penetration=True, maxc=16, max_iter=10, compute="f64", solver_eps=1e-12,
-                 not_improved_lim=3, max_trials=64, check=True, post_stab=False, force_fn=None, joints=None, broadphase=False):
+                 not_improved_lim=3, max_trials=64, check=True, post_stab=False, force_fn=None, joints=None, broadphase=False,
+                 elements=None):
         from . import contacts as _contacts
         self.post_stab = bool(post_stab)
         # `force_fn(t) -> f [B,nb,3] float32` replaces the constant force: the batched form of the reference's
@@ -659,6 +666,14 @@ class ContactWorld:
         self.p = p.to(dtype=torch.float64).contiguous()
         self.v, self.Mdiag, self.f, self.rest, self.fric = f32(v), f32(Mdiag), f32(f), f32(rest), f32(fric)
         self.B, self.nb = self.p.shape[0], self.p.shape[1]
+        # `elements` (a `force_elements.ForceSet`): state-dependent forces added onto f / force_fn(t) every step; the plain step writes
+        # their sum into ONE persistent buffer (consumed within the step), so that a captured graph replays through the same pointer
+        self.elements = elements
+        self._f_elements = None
+        if elements is not None:
+            if elements.B != self.B:
+                raise ValueError("elements are for %d scenes, the world has %d" % (elements.B, self.B))
+            self._f_elements = torch.empty(self.B, self.nb, 3, dtype=torch.float32, device=dev)
         # `joints` (a `joints.JointSet`): joints whose Jacobian follows the pose - the reference's revolute `Joint` and
         # `FixedJoint` (constraints.py:13-92) next to the X / Y / Rot / Total constraints; Je is then rebuilt on the device
         # after every move (`lcp_joint_jacobian_f64`).  `Je`: a constant Jacobian instead.
@@ -835,7 +850,7 @@ class ContactWorld:
         shape_in = tuple(t if t.requires_grad else None for t in (self.geom.radius, self.geom.verts_local))
         shape_in = shape_in if any(t is not None for t in shape_in) else ()
         c_n, c_p1, c_p2 = ct.ContactFrameFunction.apply(p_geo, self.geom, frame, self.eps, *shape_in)
-        f = self._forces()
+        f = self._forces(differentiable=True)
         count, dt_solve, sub = frame.count, self.dt, None
         if _end_t is not None:
             # u = M v + dt_k f(t) (engines.py:31-32) as the solve with dt = 1 and f_eff = float(dt_k) * f: the same fp32 value, and the
@@ -906,9 +921,15 @@ class ContactWorld:
         if js is not None:
             self._jrot_ad, self._jrot_src = new[2], self.p
 
-    def _forces(self):
-        """The forces of a step [B,nb,3] float32: the constant `f`, or `force_fn` at the scenes' clocks (forces.py:29-48)."""
-        return self.f if self.force_fn is None else self.force_fn(self.t).to(torch.float32).contiguous()
+    def _forces(self, differentiable=False):
+        """The forces of a step [B,nb,3] float32: the constant `f`, or `force_fn` at the scenes' clocks (forces.py:29-48) - plus, with
+        `elements`, their wrenches at the step's starting `p` and `v`: one launch into the persistent buffer, or (`differentiable`) one
+        `ForceElementsFunction` node on `self.p` itself - the anchors turn analytically, not through the geometry's pose."""
+        f = self.f if self.force_fn is None else self.force_fn(self.t).to(torch.float32).contiguous()
+        if self.elements is None:
+            return f
+        from .force_elements import element_forces
+        return element_forces(self.elements, self.p, self.v, f_base=f, out=None if differentiable else self._f_elements)
 
     def step(self, differentiable=False, fixed_dt=False, max_substeps=None):
         """`World.step()` = `step_dt(self.dt)` (`world.py:72-122`) for every scene.
