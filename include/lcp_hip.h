@@ -819,6 +819,46 @@ int lcp_force_elements_backward_f64(int B, int nb, int E,
                                     double* g_p, double* g_v, double* g_k, double* g_c, double* g_x0, double* g_w0,
                                     double* g_a1, double* g_a2, void* stream);
 
+/* ---- contact reports: the impulses of a solve per body, per body pair and per joint ----
+ * Which bodies touch and how hard, from the multipliers a solve wrote (z, y of lcp_solve_dynamics_f32 / lcp_step_fused_f32) and the
+ * contact records it consumed, for B scenes in one launch (lcp_report.hip).  The reference's residual is
+ * rx = A^T y + G^T z + Q x + p (lcp/solvers/pdipm.py:82-85) with Q = M, p = M v + dt f, x = -new_v, A = Je and G = [Jc; Jf; 0]
+ * (physics/engines.py:31-32,52-76), so at a solution
+ *            M (v_new - v) - dt f  =  G^T z  +  Je^T y
+ * the first term the CONTACT impulse on every body coordinate, the second the JOINT impulse.  An impulse is (torque, x, y), the order
+ * of p and v.  With the row blocks of physics/world.py:172-211, cross_2d(a, b) = ax by - ay bx and left_orthogonal(n) = (ny, -nx)
+ * (physics/utils.py:93-102), record c of a scene contributes
+ *            zn = z[c], zt = z[maxc + 2c] - z[maxc + 2c + 1], n = c_n[c], d = left_orthogonal(n), j = zn n + zt d
+ *            body c_i1[c] receives (cross_2d(c_p1[c], j), j), body c_i2[c] receives (-cross_2d(c_p2[c], j), -j).
+ *   in:  the records c_n, c_p1, c_p2 [B,maxc,2] f32, c_i1, c_i2 [B,maxc] i32; z [B,4 maxc] f32; c_count [B] i32 or NULL (every scene has
+ *        maxc records: the fused step); active [B] i32 or NULL (all active).  A scene's records are its first min(c_count, maxc); an
+ *        inactive scene (active == 0) has none, and no joint impulse either.  y [B,e] f32 and Je [B,e,3 nb] f32: either NULL, or
+ *        e == 0, leaves joint_impulse zero.  pair_first, pair_second [B,P] i32 (required when P > 0); min_impulse: the threshold of
+ *        the two counts.
+ *   out (each optional, at least one; written everywhere, never accumulated):
+ *        body_impulse[B,nb,3] f32   what the body receives from all its contacts
+ *        body_normal[B,nb] f32      the sum of zn over the records that name the body on either side (a record counts once)
+ *        body_touching[B,nb] i32    how many of those records have (double)zn > min_impulse
+ *        joint_impulse[B,nb,3] f32  sum_r Je[r, 3 b + q] y[r], rows in order
+ *        pair_impulse[B,P,3] f32    what `first` receives from `second`: records with (i1, i2) = (first, second) give
+ *                                   (cross_2d(c_p1, j), j), records with (i1, i2) = (second, first) give (-cross_2d(c_p2, j), -j);
+ *                                   the torque is about `first`'s centre
+ *        pair_normal[B,P] f32       the sum of zn over those records
+ *        pair_contacts[B,P] i32     how many of them have (double)zn > min_impulse
+ *   Every float sum is taken in fp64 in record (or row) order and rounded once at the store.  A record index outside [0, nb) gives
+ *   nothing to that side; a pair with first == second or an index outside [0, nb) is all zeros.
+ * Sizes: 1 <= nb <= 64, 1 <= maxc <= 1024, 0 <= P <= 1024, e >= 0 (LCP_E_TOOLARGE beyond the upper limits); B < 0, a size below its
+ * lower limit, a NULL record array or z, a NULL pair array with P > 0, or no output at all are LCP_E_BADARG; a refusal writes nothing.
+ * B == 0: success, no launch.  A group of lanes per scene (the power of two >= max(nb, min(maxc, 256)), at most 256; several scenes
+ * share a wavefront below 64), the records' impulses staged in LDS (48 bytes a record), every output element owned by one lane: no
+ * atomics, two runs give the same bits.  No allocation, no synchronisation, no global state. */
+int lcp_contact_report_f32(int B, int nb, int maxc, int e, int P, const int32_t* c_count, const int32_t* active,
+                           const float* c_n, const float* c_p1, const float* c_p2, const int32_t* c_i1, const int32_t* c_i2,
+                           const float* z, const float* y, const float* Je,
+                           const int32_t* pair_first, const int32_t* pair_second, double min_impulse,
+                           float* body_impulse, float* body_normal, int32_t* body_touching, float* joint_impulse,
+                           float* pair_impulse, float* pair_normal, int32_t* pair_contacts, void* stream);
+
 /* ---- the breakout encoder: frames -> paddle, blocks and ball of every scene ----
  * What extract_params (experiments/breakout/encoder.py:63-133, with remove_rect :136-137 and get_pos_dims :140-145) reads off
  * an Atari Breakout frame, for B frames in one launch (lcp_encoder.hip).  The reference reads channel 0 only (`frame[..., 0]`):

@@ -904,6 +904,23 @@ int lcp_force_elements_backward_f64(int B, int nb, int E, const int32_t* kind, c
                                              g_w0, g_a1, g_a2, stream);
 }
 
+int lcp_contact_report_f32(int B, int nb, int maxc, int e, int P, const int32_t* c_count, const int32_t* active, const float* c_n,
+                           const float* c_p1, const float* c_p2, const int32_t* c_i1, const int32_t* c_i2, const float* z, const float* y,
+                           const float* Je, const int32_t* pair_first, const int32_t* pair_second, double min_impulse,
+                           float* body_impulse, float* body_normal, int32_t* body_touching, float* joint_impulse, float* pair_impulse,
+                           float* pair_normal, int32_t* pair_contacts, void* stream) {
+  if (B < 0 || nb < 1 || maxc < 1 || e < 0 || P < 0) return LCP_E_BADARG;
+  if (!c_n || !c_p1 || !c_p2 || !c_i1 || !c_i2 || !z) return LCP_E_BADARG;
+  if (P > 0 && (!pair_first || !pair_second)) return LCP_E_BADARG;
+  if (!body_impulse && !body_normal && !body_touching && !joint_impulse && !pair_impulse && !pair_normal && !pair_contacts)
+    return LCP_E_BADARG;
+  if (!lcp::contact_report_supported(nb, maxc, P)) return LCP_E_TOOLARGE;
+  if (B == 0) return 0;
+  return lcp::contact_report_launch(B, nb, maxc, e, P, c_count, active, c_n, c_p1, c_p2, c_i1, c_i2, z, y, Je, pair_first, pair_second,
+                                    min_impulse, body_impulse, body_normal, body_touching, joint_impulse, pair_impulse, pair_normal,
+                                    pair_contacts, stream);
+}
+
 // the layout words of lcp_extract_params_u8 against an H x W image (include/lcp_hip.h lists what is refused)
 static bool encoder_layout_ok(const int32_t* w, int H, int W) {
   const int paddle_line = w[0], paddle_h = w[1], paddle_w = w[2], paddle_key = w[3], ball_w = w[4], nrows = w[5], band_top = w[6],

@@ -322,6 +322,14 @@ int force_elements_backward_launch(int B, int nb, int E, const int32_t* kind, co
                                    const double* limit, const double* p, const float* v, const float* g_f, double* g_p, double* g_v,
                                    double* g_k, double* g_c, double* g_x0, double* g_w0, double* g_a1, double* g_a2, void* stream);
 
+// lcp_report.hip: the contact report (include/lcp_hip.h, "contact reports"); arguments checked by the caller
+bool contact_report_supported(int nb, int maxc, int P);                           // 1 <= nb <= 64, 1 <= maxc <= 1024, 0 <= P <= 1024
+int contact_report_launch(int B, int nb, int maxc, int e, int P, const int32_t* c_count, const int32_t* active, const float* c_n,
+                          const float* c_p1, const float* c_p2, const int32_t* c_i1, const int32_t* c_i2, const float* z, const float* y,
+                          const float* Je, const int32_t* pair_first, const int32_t* pair_second, double min_impulse, float* body_impulse,
+                          float* body_normal, int32_t* body_touching, float* joint_impulse, float* pair_impulse, float* pair_normal,
+                          int32_t* pair_contacts, void* stream);
+
 // lcp_encoder.hip: the breakout encoder (experiments/breakout/encoder.py:63-145), one workgroup per frame; arguments checked by
 // the caller, `layout` the LCP_ENC_LAYOUT_WORDS host words
 int extract_params_launch(int B, int H, int W, const uint8_t* frame, long long stride_b, long long stride_row, long long stride_col,

@@ -638,12 +638,18 @@ class ContactWorld:
     `solve_dynamics`; `fixed_dt=True` evaluates again in every sub-step), differentiable to `p`, `v`, `f` and the elements' parameters in
     `step(differentiable=True)`.  The coupling is explicit: a spring of stiffness k on a mass m is stable only while
     `dt sqrt(k / m) < 2` (a damper c: `dt c / m < 2`) - stiffer elements need a smaller `dt`; nothing here integrates them implicitly.
+    `report=True | PairSet` (physics/contact_report.py) keeps `world.report`, one persistent `ContactReport`: the contact impulse every body
+    received in the last step (and every pair of the `PairSet`), how many records pushed, and the joint impulse - one launch of
+    `lcp_contact_report_f32` per solve, between the solve and the detection that overwrites the records it consumed; `fixed_dt=True` sums
+    the impulses over the sub-steps and keeps the largest counts, so that `impulse / dt` is the mean force over the interval.
+    `report_min_impulse`: the normal multiplier above which a record counts as pushing.  The correction of `post_stab` moves positions and
+    is not reported; the tensors carry no gradient.
     """
 
     def __init__(self, geom, p, v, Mdiag, f, rest, fric, Je=None, dt=1.0 / 30, eps=0.1, tol=1e-6,
                  strict_no_penetration=True, maxc=16, max_iter=10, compute="f64", solver_eps=1e-12,
                  not_improved_lim=3, max_trials=64, check=True, post_stab=False, force_fn=None, joints=None, broadphase=False,
-                 elements=None):
+                 elements=None, report=None, report_min_impulse=0.0):
         from . import contacts as _contacts
         self.post_stab = bool(post_stab)
         # `force_fn(t) -> f [B,nb,3] float32` replaces the constant force: the batched form of the reference's
@@ -674,6 +680,17 @@ class ContactWorld:
             if elements.B != self.B:
                 raise ValueError("elements are for %d scenes, the world has %d" % (elements.B, self.B))
             self._f_elements = torch.empty(self.B, self.nb, 3, dtype=torch.float32, device=dev)
+        # `report` (True, or a `proximity.PairSet` for the pair part): ONE persistent `ContactReport`, so that a captured graph replays
+        # through the same pointers; `_report_sub` receives a sub-step's launch in fixed-interval steps, which fold it into `report`
+        self.report = self._report_sub = self._report_pairs = None
+        self.report_min_impulse = float(report_min_impulse)
+        if report is not None and report is not False:
+            from .contact_report import ContactReport
+            if report is not True:
+                if report.first.shape[0] != self.B:
+                    raise ValueError("the report's pairs are for %d scenes, the world has %d" % (report.first.shape[0], self.B))
+                self._report_pairs = report
+            self.report = ContactReport.zeros(self.B, self.nb, 0 if report is True else report.first.shape[1], dev)
         # `joints` (a `joints.JointSet`): joints whose Jacobian follows the pose - the reference's revolute `Joint` and
         # `FixedJoint` (constraints.py:13-92) next to the X / Y / Rot / Total constraints; Je is then rebuilt on the device
         # after every move (`lcp_joint_jacobian_f64`).  `Je`: a constant Jacobian instead.
@@ -730,6 +747,8 @@ class ContactWorld:
         self.t.fill_(float(t))
         self.behind.zero_()
         self.sticky_status.zero_()              # (a device op: an overflow of an earlier roll-out must not fail this one's check)
+        if self.report is not None:
+            self.report.zero_()                 # (no step has been taken from the new pose)
         # nothing of the recorded steps before describes the new pose (`_autograd_owned` stays as it is: a world that has recorded steps
         # goes on copying its state before the next plain step - one copy too many at the worst)
         self._p_geom = self._p_geom_src = self._jrot_ad = self._jrot_src = None
@@ -876,6 +895,8 @@ class ContactWorld:
             self.substeps += sub["active"]
         out = opts["last"]
         torch.bitwise_or(self.sticky_status, out["status"], out=self.sticky_status)
+        if self.report is not None:                                        # (values only: the report has no gradient)
+            self._fill_report(frame, out, count, sub)
         ct.move_and_find_contacts(self.geom, self.p.detach(), v_new.detach(), self.dt, eps=self.eps, tol=self.tol,
                                   strict=self.strict, dt_floor=self.dt / 4, max_trials=self.max_trials, t=self.t, out=cb,
                                   dt_scene=None if sub is None else sub["dt_k"], **self._bp)
@@ -931,6 +952,21 @@ class ContactWorld:
         from .force_elements import element_forces
         return element_forces(self.elements, self.p, self.v, f_base=f, out=None if differentiable else self._f_elements)
 
+    def _fill_report(self, frame, out, count, sub):
+        """`self.report` from the solve that has just run on `frame` (its multipliers in `out`, its joint Jacobian still in `self.Je`):
+        one launch.  `sub` (a sub-step of a fixed-interval step): the launch gets the sub-step's counts and active scenes and is folded
+        into the interval's report, which `_step_fixed` zeroed."""
+        from .contact_report import ContactReport, contact_report
+        Je = None if self.Je is None else self.Je.detach()
+        kw = dict(y=out["y"], Je=Je, pairs=self._report_pairs, min_impulse=self.report_min_impulse)
+        if sub is None:
+            contact_report(frame, out["z"], count=count, out=self.report, **kw)
+            return
+        if self._report_sub is None:
+            self._report_sub = ContactReport.zeros(self.B, self.nb, self.report.P, self.p.device)
+        contact_report(frame, out["z"], count=count, active=sub["active"], out=self._report_sub, **kw)
+        self.report.accumulate_(self._report_sub)
+
     def step(self, differentiable=False, fixed_dt=False, max_substeps=None):
         """`World.step()` = `step_dt(self.dt)` (`world.py:72-122`) for every scene.
         `fixed_dt=True`: `World.step(fixed_dt=True)` (`world.py:72-80`) - every scene repeats `step_dt(end_t - t)` until its clock
@@ -958,6 +994,8 @@ class ContactWorld:
         else:
             end_t = torch.add(self.t, self.dt, out=self._end_t)
         self.substeps.zero_()
+        if self.report is not None:
+            self.report.zero_()
         k = 0
         while True:
             if max_substeps is None:
@@ -999,6 +1037,8 @@ class ContactWorld:
                              max_iter=self.max_iter, compute=self.compute, ws=self._ws, out=self._out, pinned=self._pinned)
         self._ws, self._out = out["ws"], out
         torch.bitwise_or(self.sticky_status, out["status"], out=self.sticky_status)
+        if self.report is not None:                                      # before the detection overwrites the records in `cb`
+            self._fill_report(cb, out, count, sub)
         self.v, out["v_new"] = out["v_new"], self.v                      # world.py:87 set_v(new_v)
         if fixed:
             substep_commit(sub["active"], out["v_new"], self.v)          # ... which a finished scene does not reach
