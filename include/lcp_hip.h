@@ -774,6 +774,76 @@ int lcp_pair_distance_backward_f64(int B, int nb, int nvcap, int scene_verts_max
                                    const double* g_dist,
                                    double* g_p, double* g_radius, double* g_verts_local, void* stream);
 
+/* ---- time of impact: when body pairs first touch along the engine's move, differentiable ----
+ * A step accepts a move whose END pose does not penetrate; a body that travels more than an obstacle's thickness in one dt lands
+ * beyond it without a record.  This query says when P pairs per scene first come within a margin of each other along the move, for
+ * B scenes in one launch (lcp_toi.hip).  The scene inputs and their limits are those of lcp_pair_distance_f64.
+ *   motion:  pose_b(t) = p_b + t (double)v_b in all three coordinates (bodies.py:80-82) for 0 <= t <= horizon; p[B,nb,3] f64 (rot, x,
+ *            y), v[B,nb,3] f32 (w, vx, vy).  d(t): dist of lcp_pair_distance_f64 for the pair at pose(t), without a cutoff; n(t): its
+ *            unit normal from body 1 towards body 2.
+ *   pairs, P per scene: pair_first[B,P] i32, pair_second[B,P] i32, margin[B,P] f64 >= 0;  per scene: horizon[B] f64;
+ *            tol > 0 (a distance), 1 <= max_iter <= 1024 (evaluations of d).
+ *   conservative advancement: t_0 = 0; for k = 0, 1, ...
+ *            d_k = d(t_k), n_k = n(t_k)
+ *            d_k - margin <= tol:   TOUCHING with toi = 0 when k == 0, else HIT with toi = t_k
+ *            a_k = -n_k . (vlin_2 - vlin_1) + |w_1| rho_1 + |w_2| rho_2     rho: 0 for a circle, max_j |verts_local_j| for a hull
+ *            a_k <= 0:              MISS
+ *            t_k+1 = t_k + (d_k - margin) / a_k;   t_k+1 >= horizon:  MISS
+ *            after max_iter evaluations without an exit: UNCONVERGED, toi = the last evaluated t_k.
+ *       Why no iterate passes the first touch: for separated convex bodies n_k is a separating direction - at t_k body 1 lies in
+ *       {x : n_k . x <= s} and body 2 in {x : n_k . x >= s + d_k}.  Along n_k a point of body i moves at n_k . vlin_i plus at most
+ *       |w_i| rho_i (it turns about the centre at a distance of at most rho_i; a circle's surface does not move when it turns).  So
+ *       after s - t_k more time the gap between the two half planes, and with it the distance, is at least d_k - (s - t_k) a_k:
+ *               d(s) >= d_k - (s - t_k) a_k   for every s >= t_k,
+ *       which stays above margin until t_k+1.  By induction no t_k lies beyond the first time d reaches margin: a HIT has
+ *       margin <= d <= margin + tol at a time no later than the first touch, an UNCONVERGED toi is a true lower bound of it, and a
+ *       MISS (a_k <= 0: the gap cannot shrink; t_k+1 >= horizon) has no touch before the horizon.
+ *   results: MISS returns toi = horizon.  status: LCP_TOI_MISS 0, LCP_TOI_HIT 1, LCP_TOI_TOUCHING 2, LCP_TOI_UNCONVERGED 3.
+ *   invalid: pair_first == pair_second, an index outside [0, nb), or a hull of fewer than three vertices: MISS without evaluation.
+ *   a scene with more hull vertices than scene_verts_max, or with a horizon that is <= 0 or NaN, is not queried: every pair is a MISS
+ *            with toi = max(horizon, 0) (0 for a NaN), and first_toi is that value.
+ *   cull:    a pair whose bounding circles (a circle's radius; a hull's rho about its centre) are at least
+ *            margin + horizon (|vlin_2 - vlin_1| + |w_1| rho_1 + |w_2| rho_2) apart, and more than margin + tol, is a MISS without
+ *            evaluation: then d_0 - margin > tol and t_1 >= horizon, the rule's own first iteration.  No result depends on the cull.
+ *   out (each optional, at least one; written, never accumulated): toi[B,P] f64, status[B,P] i32, normal[B,P,2] f64 (n at toi for HIT
+ *            and TOUCHING, else 0), and per scene first_toi[B] f64, first_pair[B] i32: the smallest toi over the pairs with status HIT
+ *            or UNCONVERGED and its pair, the smallest pair index on ties; none: horizon and -1.  (TOUCHING pairs are left out on
+ *            purpose: they are in the contact list already.)
+ * Sizes: those of lcp_pair_distance_f64 (1 <= nb <= 64, 8 <= nvcap <= 64, 0 <= scene_verts_max <= 1024, 1 <= P <= 1024), B >= 0; a NULL
+ * input array, no output, tol or max_iter outside their range - anything else is LCP_E_BADARG before any launch.  B == 0: success, no
+ * launch.  fp64 arithmetic.  One workgroup per scene, lane = pair, 256 pairs at a time; staged in LDS is what does not move (the
+ * body-frame vertices, rho, p, v), every evaluation turns the two bodies to the lane's own time.  No allocation, no synchronisation, no
+ * global state. */
+#define LCP_TOI_MISS 0
+#define LCP_TOI_HIT 1
+#define LCP_TOI_TOUCHING 2
+#define LCP_TOI_UNCONVERGED 3
+int lcp_time_of_impact_f64(int B, int nb, int nvcap, int scene_verts_max, int P,
+                           const int32_t* kind, const double* radius, const double* verts_local, const int32_t* nverts,
+                           const double* p, const float* v,
+                           const int32_t* pair_first, const int32_t* pair_second, const double* margin, const double* horizon,
+                           double tol, int max_iter,
+                           double* toi, int32_t* status, double* normal, double* first_toi, int32_t* first_pair, void* stream);
+
+/* Backward of toi of lcp_time_of_impact_f64.  The forward is iterative; the backward needs ONE evaluation, at pose(toi).
+ *   in: the scene, v and the pairs as above; toi[B,P] f64 and status[B,P] i32 as the forward wrote them; g_toi[B,P] f64 (all required).
+ *   out (each optional, at least one; f64, written everywhere, never accumulated): g_p[B,nb,3], g_v[B,nb,3], g_radius[B,nb] (hulls: 0),
+ *       g_verts_local[B,nb,nvcap,2] (body frame; circles and slots >= nverts: 0), g_margin[B,P].
+ * A pair is live when its status is HIT and ddot < 0, ddot = n . (V_2(W_2) - V_1(W_1)) with V_i(W) = vlin_i + w_i perp(W - c_i) the
+ * velocities of the witness points W_1, W_2 of the distance rule at pose(toi), perp(x, y) = (-y, x).  From d(pose(toi)) = margin:
+ *       d(toi) = (d(margin) - [n . (dW_2 - dW_1) - dr_1 - dr_2]) / ddot
+ *   dW: as in lcp_pair_distance_backward_f64 but at the advanced pose: dW = dc + toi dvlin + (drot + toi dw) perp(W - c)
+ *       + R(rot + w toi) dv_local (an edge's point: (1 - t) and t of it at the edge's two vertices).  So g_v is, pair by pair, toi times
+ *       the pair's g_p terms.  Pairs that are not live give exactly 0 to every output.
+ * One workgroup per scene, the live pairs' terms staged in LDS (104 bytes a pair), every body owned by one wavefront that walks the
+ * pairs in order - no atomics, two runs give the same bits whichever outputs are asked for. */
+int lcp_time_of_impact_backward_f64(int B, int nb, int nvcap, int scene_verts_max, int P,
+                                    const int32_t* kind, const double* radius, const double* verts_local, const int32_t* nverts,
+                                    const double* p, const float* v,
+                                    const int32_t* pair_first, const int32_t* pair_second,
+                                    const double* toi, const int32_t* status, const double* g_toi,
+                                    double* g_p, double* g_v, double* g_radius, double* g_verts_local, double* g_margin, void* stream);
+
 /* ---- force elements: springs, motors and drag as a function of the state, differentiable ----
  * Forces that depend on the state of the scene - a spring or damper between two anchors, a PD servo on a relative angle, viscous
  * drag - for E elements per scene and B scenes in one launch (lcp_forces.hip), added onto an optional base force.

@@ -92,6 +92,10 @@ SIGNATURES = {
     # the proximity queries: sizes, the scene, the pairs (first, second, max_dist), then the outputs
     "lcp_pair_distance_f64": (_I, [_I] * 5 + [_P] * 5 + [_P] * 3 + [_P] * 4 + [_P]),
     "lcp_pair_distance_backward_f64": (_I, [_I] * 5 + [_P] * 5 + [_P] * 3 + [_P] + [_P] * 3 + [_P]),
+    # the time of impact: sizes, the scene with v, the pairs (first, second), margin, horizon, tol, max_iter, then the outputs; the
+    # backward: toi, status, g_toi, then the gradients
+    "lcp_time_of_impact_f64": (_I, [_I] * 5 + [_P] * 6 + [_P] * 2 + [_P] * 2 + [_c.c_double, _I] + [_P] * 5 + [_P]),
+    "lcp_time_of_impact_backward_f64": (_I, [_I] * 5 + [_P] * 6 + [_P] * 2 + [_P] * 3 + [_P] * 5 + [_P]),
     # the force elements: sizes, the elements (kind, b1, b2, a1, a2, k, c, x0, w0, limit), p, v, then f_base, f_out / g_f and the gradients
     "lcp_force_elements_f64": (_I, [_I] * 3 + [_P] * 10 + [_P] * 2 + [_P] * 2 + [_P]),
     "lcp_force_elements_backward_f64": (_I, [_I] * 3 + [_P] * 10 + [_P] * 2 + [_P] + [_P] * 8 + [_P]),

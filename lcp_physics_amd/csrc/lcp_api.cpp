@@ -877,6 +877,40 @@ int lcp_pair_distance_backward_f64(int B, int nb, int nvcap, int scene_verts_max
                                             pair_second, pair_max_dist, g_dist, g_p, g_radius, g_verts_local, stream);
 }
 
+// what both time-of-impact entries refuse before any launch: what the proximity entries refuse, with the velocities among the scene arrays
+static bool time_of_impact_args_ok(int B, int nb, int nvcap, int scene_verts_max, int P, const void* kind, const void* radius,
+                                   const void* verts_local, const void* nverts, const void* p, const void* v, const void* pair_first,
+                                   const void* pair_second) {
+  if (B < 0 || !lcp::time_of_impact_supported(nb, nvcap, scene_verts_max, P)) return false;
+  return kind && radius && verts_local && nverts && p && v && pair_first && pair_second;
+}
+
+int lcp_time_of_impact_f64(int B, int nb, int nvcap, int scene_verts_max, int P, const int32_t* kind, const double* radius,
+                           const double* verts_local, const int32_t* nverts, const double* p, const float* v, const int32_t* pair_first,
+                           const int32_t* pair_second, const double* margin, const double* horizon, double tol, int max_iter, double* toi,
+                           int32_t* status, double* normal, double* first_toi, int32_t* first_pair, void* stream) {
+  if (!time_of_impact_args_ok(B, nb, nvcap, scene_verts_max, P, kind, radius, verts_local, nverts, p, v, pair_first, pair_second))
+    return LCP_E_BADARG;
+  if (!margin || !horizon || !(tol > 0.0) || max_iter < 1 || max_iter > 1024) return LCP_E_BADARG;      // (a NaN tol fails too)
+  if (!toi && !status && !normal && !first_toi && !first_pair) return LCP_E_BADARG;                     // (nothing asked for)
+  if (B == 0) return 0;
+  return lcp::time_of_impact_launch(B, nb, nvcap, scene_verts_max, P, kind, radius, verts_local, nverts, p, v, pair_first, pair_second,
+                                    margin, horizon, tol, max_iter, toi, status, normal, first_toi, first_pair, stream);
+}
+
+int lcp_time_of_impact_backward_f64(int B, int nb, int nvcap, int scene_verts_max, int P, const int32_t* kind, const double* radius,
+                                    const double* verts_local, const int32_t* nverts, const double* p, const float* v,
+                                    const int32_t* pair_first, const int32_t* pair_second, const double* toi, const int32_t* status,
+                                    const double* g_toi, double* g_p, double* g_v, double* g_radius, double* g_verts_local,
+                                    double* g_margin, void* stream) {
+  if (!time_of_impact_args_ok(B, nb, nvcap, scene_verts_max, P, kind, radius, verts_local, nverts, p, v, pair_first, pair_second))
+    return LCP_E_BADARG;
+  if (!toi || !status || !g_toi || (!g_p && !g_v && !g_radius && !g_verts_local && !g_margin)) return LCP_E_BADARG;
+  if (B == 0) return 0;
+  return lcp::time_of_impact_backward_launch(B, nb, nvcap, scene_verts_max, P, kind, radius, verts_local, nverts, p, v, pair_first,
+                                             pair_second, toi, status, g_toi, g_p, g_v, g_radius, g_verts_local, g_margin, stream);
+}
+
 // what both force-element entries refuse before any launch: a negative batch, sizes outside the limits, a missing element or state array
 static bool force_elements_args_ok(int B, int nb, int E, const void* kind, const void* b1, const void* b2, const void* a1, const void* a2,
                                    const void* k, const void* c, const void* x0, const void* w0, const void* limit, const void* p,

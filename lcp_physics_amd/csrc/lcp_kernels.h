@@ -312,6 +312,19 @@ int pair_distance_backward_launch(int B, int nb, int nvcap, int scene_verts_max,
                                   const int32_t* pair_second, const double* pair_max_dist, const double* g_dist, double* g_p,
                                   double* g_radius, double* g_verts_local, void* stream);
 
+// lcp_toi.hip: the time of impact of body pairs along the move p + t v (include/lcp_hip.h, "time of impact") and the backward of the
+// times; arguments checked by the caller
+bool time_of_impact_supported(int nb, int nvcap, int scene_verts_max, int P);     // render_supported and 1 <= P <= 1024
+int time_of_impact_launch(int B, int nb, int nvcap, int scene_verts_max, int P, const int32_t* kind, const double* radius,
+                          const double* verts_local, const int32_t* nverts, const double* p, const float* v, const int32_t* pair_first,
+                          const int32_t* pair_second, const double* margin, const double* horizon, double tol, int max_iter, double* toi,
+                          int32_t* status, double* normal, double* first_toi, int32_t* first_pair, void* stream);
+int time_of_impact_backward_launch(int B, int nb, int nvcap, int scene_verts_max, int P, const int32_t* kind, const double* radius,
+                                   const double* verts_local, const int32_t* nverts, const double* p, const float* v,
+                                   const int32_t* pair_first, const int32_t* pair_second, const double* toi, const int32_t* status,
+                                   const double* g_toi, double* g_p, double* g_v, double* g_radius, double* g_verts_local, double* g_margin,
+                                   void* stream);
+
 // lcp_forces.hip: the force elements (include/lcp_hip.h, "force elements") and their backward; arguments checked by the caller
 bool force_elements_supported(int nb, int E);                                     // 1 <= nb <= 64 and 1 <= E <= 1024
 int force_elements_launch(int B, int nb, int E, const int32_t* kind, const int32_t* b1, const int32_t* b2, const double* a1,

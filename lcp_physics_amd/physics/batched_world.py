@@ -644,12 +644,18 @@ class ContactWorld:
     the impulses over the sub-steps and keeps the largest counts, so that `impulse / dt` is the mean force over the interval.
     `report_min_impulse`: the normal multiplier above which a record counts as pushing.  The correction of `post_stab` moves positions and
     is not reported; the tensors carry no gradient.
+    `ccd=True | PairSet` (physics/impact.py) makes a step never move past a first touch: after the solve, one launch of
+    `lcp_time_of_impact_f64` on the pose the step starts from and the new velocities, and the move starts from `min(dt, first impact)`
+    of these pairs (True: all pairs, up to 45 bodies, without those `geom.no_contact` excludes) instead of `dt` - a clipped step is an
+    ordinary short step (`dt_used`), `fixed_dt=True` makes up the remainder in further sub-steps.  `ccd_margin` (default `eps / 2`): the
+    distance at which the move ends, within the detection's `eps`, so that the next solve sees the contact.  No gradient through the
+    clipped dt.  `time_to_contact(pairs)` is the query itself at the world's `p` and `v`.
     """
 
     def __init__(self, geom, p, v, Mdiag, f, rest, fric, Je=None, dt=1.0 / 30, eps=0.1, tol=1e-6,
                  strict_no_penetration=True, maxc=16, max_iter=10, compute="f64", solver_eps=1e-12,
                  not_improved_lim=3, max_trials=64, check=True, post_stab=False, force_fn=None, joints=None, broadphase=False,
-                 elements=None, report=None, report_min_impulse=0.0):
+                 elements=None, report=None, report_min_impulse=0.0, ccd=None, ccd_margin=None):
         from . import contacts as _contacts
         self.post_stab = bool(post_stab)
         # `force_fn(t) -> f [B,nb,3] float32` replaces the constant force: the batched form of the reference's
@@ -729,12 +735,46 @@ class ContactWorld:
         self.broadphase = bool(broadphase)
         self.candidates = torch.zeros(self.B, dtype=torch.int32, device=dev) if self.broadphase else None
         self._bp = {"broadphase": True, "candidates": self.candidates} if self.broadphase else {}
+        # `ccd` (True: all pairs, or a `proximity.PairSet`): ONE persistent `impact.FirstImpact`, so that a captured graph replays through
+        # the same pointers; every move then starts from min(dt, the first time of impact of these pairs)
+        self._ccd = None
+        if ccd is not None and ccd is not False:
+            from .impact import FirstImpact
+            pairs = self._ccd_all_pairs() if ccd is True else ccd
+            if pairs.B != self.B:
+                raise ValueError("the ccd pairs are for %d scenes, the world has %d" % (pairs.B, self.B))
+            self._ccd = FirstImpact(geom, pairs, self.eps / 2 if ccd_margin is None else ccd_margin)
+        elif ccd_margin is not None:
+            raise ValueError("ccd_margin belongs to ccd")
         # world.py:65-66: contacts of the initial pose; :67-70: refuse interpenetration at start
         self.contacts = _contacts.find_contacts(geom, self.p, maxc=self.maxc, eps=self.eps, **self._bp)
         if check:
             self.check_capacity()
             if self.strict and bool((self.contacts.max_pen > self.tol).any()):
                 raise AssertionError("Interpenetration at start (world.py:68-70)")
+
+    CCD_MAX_BODIES = 45                  # 990 pairs; 46 bodies have 1035, more than one query takes
+
+    def _ccd_all_pairs(self):
+        """Every pair i < j of the world's bodies on its device; the pairs `geom.no_contact` excludes are made invalid pairs (second =
+        first), which the query answers MISS without evaluation."""
+        from .proximity import PairSet
+        if self.nb > self.CCD_MAX_BODIES:
+            raise ValueError("ccd=True covers all pairs of at most %d bodies (got %d): give a PairSet" % (self.CCD_MAX_BODIES, self.nb))
+        pairs = PairSet.all_pairs(self.nb, self.B).to(self.p.device)
+        nc = self.geom.no_contact
+        if nc is not None:
+            i, j = pairs.first[0].long(), pairs.second[0].long()
+            off = (nc[:, i, j] != 0) | (nc[:, j, i] != 0)
+            pairs = PairSet(pairs.first, torch.where(off, pairs.first, pairs.second).contiguous(), pairs.max_dist)
+        return pairs
+
+    def _ccd_dt(self, v, dt_k):
+        """The per-scene dt the move after a solve starts with: `dt_k` (a sub-step's [B], or None for `self.dt`) in a world without
+        `ccd`; else clipped at the first time of impact of the `ccd` pairs, from the pose the step starts at with the NEW velocities."""
+        if self._ccd is None:
+            return dt_k
+        return self._ccd(self.p.detach(), v, self.dt if dt_k is None else dt_k)
 
     def restart(self, p, v=None, jrot1=None, t=0.0):
         """Put the world back at pose `p` [B,nb,3] with velocities `v` (default: at rest), joint angles `jrot1` (default: those
@@ -899,7 +939,7 @@ class ContactWorld:
             self._fill_report(frame, out, count, sub)
         ct.move_and_find_contacts(self.geom, self.p.detach(), v_new.detach(), self.dt, eps=self.eps, tol=self.tol,
                                   strict=self.strict, dt_floor=self.dt / 4, max_trials=self.max_trials, t=self.t, out=cb,
-                                  dt_scene=None if sub is None else sub["dt_k"], **self._bp)
+                                  dt_scene=self._ccd_dt(v_new.detach().contiguous(), None if sub is None else sub["dt_k"]), **self._bp)
         # the accepted pose: the kernel's value, the gradient of p + v dt_used (a zero rotation increment carries no gradient to the geometry)
         self.v = v_new
         if js is not None:                                                 # joint.move(dt): rot1 += body1.v[0] dt (constraints.py:39-43)
@@ -1046,7 +1086,7 @@ class ContactWorld:
         self._contacts_mod.move_and_find_contacts(self.geom, self.p, self.v, self.dt, eps=self.eps, tol=self.tol,
                                                   strict=self.strict, dt_floor=self.dt / 4,
                                                   max_trials=self.max_trials, t=self.t, out=cb,
-                                                  dt_scene=sub["dt_k"] if fixed else None, **self._bp)
+                                                  dt_scene=self._ccd_dt(self.v, sub["dt_k"] if fixed else None), **self._bp)
         self.p, cb.p_out = cb.p_out, self.p                              # accepted pose becomes the state (double buffer)
         if self.joints is not None:                                      # joint.move(dt) + the Jacobian at the new pose (world.py:91-92)
             self._Je_spare = self.joints.jacobian(self.p, v=self.v, dt_scene=cb.dt_used, out=self._Je_spare)
@@ -1106,3 +1146,10 @@ class ContactWorld:
         `step(differentiable=True)` the distances are part of the roll-out's graph."""
         from .proximity import pair_distances
         return pair_distances(self.geom, self.p, pairs, **kw)
+
+    def time_to_contact(self, pairs, horizon=None, **kw):
+        """When the body pairs of every scene first touch if every body keeps its velocity, `(toi [B,P] f64, status [B,P] int32)`
+        (`physics.impact.time_of_impact(self.geom, self.p, self.v, pairs, horizon, **kw)`; `horizon` defaults to `dt`).  After
+        `step(differentiable=True)` the times are part of the roll-out's graph."""
+        from .impact import time_of_impact
+        return time_of_impact(self.geom, self.p, self.v, pairs, self.dt if horizon is None else horizon, **kw)
