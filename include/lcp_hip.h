@@ -774,6 +774,57 @@ int lcp_pair_distance_backward_f64(int B, int nb, int nvcap, int scene_verts_max
                                    const double* g_dist,
                                    double* g_p, double* g_radius, double* g_verts_local, void* stream);
 
+/* ---- point probes: the signed distance from query points to the scene, differentiable ----
+ * How far a point is from the scene - negative inside a body - and from which body, for N points per scene and B scenes in one
+ * launch (lcp_points.hip).  A point is mounted on a body (or on the world frame) and tests every other body or one target body.  The
+ * scene inputs, their limits and the world vertices w_i, edges e_i = w_i+1 - w_i and outward unit normals n_i are exactly those of
+ * lcp_render_f64 / lcp_cast_rays_f64; a scene with more hull vertices than scene_verts_max is not probed (every point is void), a
+ * hull of fewer than three vertices is never a candidate.  no_contact is not consulted.
+ *   points, N per scene: pt_body[B,N] i32 (the mounting body m; -1: the world frame; any other value outside [0, nb): the point is
+ *       void), pt_xy[B,N,2] f64 in the mounting frame, pt_target[B,N] i32 (-1: every body is tested; k in [0, nb): body k alone; any
+ *       other value: no candidate), pt_max_dist[B,N] f64 > 0 (+inf allowed).
+ *       x = c_m + R(rot_m) xy; world frame: x = xy.  A point never tests its own mounting body: target == m gives no candidate.
+ *   per candidate body k: (d_k, u_k, edge, t)
+ *       circle  q = x - c, d = |q| - r, u = q / |q| (exactly 0 when |q| == 0).
+ *       hull    the signed distance of the hull at x with its derivative data ("circle 1 - hull 2" above with r1 = 0): outside, the
+ *               edge of smallest squared point-to-segment distance (the first on ties), t clamped to [0, 1], d = |x - foot|,
+ *               u = (x - foot) / d; inside (max_i h_i <= 0, h_i = n_i . (x - w_i)) the edge of largest h_i (the first i on ties),
+ *               d = h_i, u = n_i, t = (x - w_i) . e_i / |e_i|^2 unclamped.
+ *   per point: the smallest d_k, on ties the smallest k.  None, or d >= pt_max_dist: dist = pt_max_dist, body = -1, normal = 0 - a
+ *       void point, without a gradient.  Otherwise dist = d (negative inside), body = k, normal = u = d(dist)/dx.
+ *   out (each optional, at least one; written everywhere, never accumulated): dist[B,N] f64, body[B,N] i32, normal[B,N,2] f64.
+ * Sizes: those of lcp_cast_rays_f64 (1 <= nb <= 64, 8 <= nvcap <= 64, 0 <= scene_verts_max <= 1024), 1 <= N <= 1024, B >= 0; a NULL
+ * scene or point array, no output - anything else is LCP_E_BADARG before any launch.  B == 0: success, no launch.  fp64 arithmetic.
+ * One workgroup per (scene, 256 points), lane = point; a body whose bounding circle lies at or beyond min(the best distance so far,
+ * pt_max_dist) for every point of a wavefront is skipped by that wavefront, where the rule gives no change: a finite cutoff leaves
+ * the bits of every live point what +inf gives.  No allocation, no synchronisation, no global state. */
+int lcp_point_distance_f64(int B, int nb, int nvcap, int scene_verts_max, int N,
+                           const int32_t* kind, const double* radius, const double* verts_local, const int32_t* nverts,
+                           const double* p,
+                           const int32_t* pt_body, const double* pt_xy, const int32_t* pt_target, const double* pt_max_dist,
+                           double* dist, int32_t* body, double* normal, void* stream);
+
+/* Backward of dist of lcp_point_distance_f64.  Same inputs and checks; nothing is saved by the forward, every point's selection is
+ * recomputed.
+ *   in: g_dist[B,N] f64 (required).
+ *   out (each optional, at least one; written, never accumulated): g_p[B,nb,3] f64, g_radius[B,nb] f64 (hulls: exactly 0),
+ *       g_verts_local[B,nb,nvcap,2] f64 (body frame; circles and slots >= nverts: exactly 0), g_pt_xy[B,N,2] f64 (mounting frame).
+ * A live point differentiates by
+ *       dd = u . (dx - dX) - dr
+ *   dx = dc_m + drot_m perp(x - c_m) + R(rot_m) d(xy)   (world frame: d(xy)),  perp(x, y) = (-y, x);
+ *   dX = dc_k (a circle; dr: its radius' change)
+ *      = (1 - t) dw_i + t dw_i+1 with dw = dc_k + drot_k perp(w - c_k) + R(rot_k) dv_local   (a hull; dr = 0).
+ * Inside a hull t is unclamped, which makes the face term exact: the normal's rotation contributes -t n . (dw_i+1 - dw_i).  Void
+ * points have zero gradient.  A body collects from every point whose `body` it is and from every point mounted on it: one workgroup
+ * per scene, the points' terms staged in LDS behind the scene (52 bytes a point), every body owned by one wavefront that sums over
+ * the points in order - no atomics, two runs give the same bits.  g_pt_xy is the point's own. */
+int lcp_point_distance_backward_f64(int B, int nb, int nvcap, int scene_verts_max, int N,
+                                    const int32_t* kind, const double* radius, const double* verts_local, const int32_t* nverts,
+                                    const double* p,
+                                    const int32_t* pt_body, const double* pt_xy, const int32_t* pt_target, const double* pt_max_dist,
+                                    const double* g_dist,
+                                    double* g_p, double* g_radius, double* g_verts_local, double* g_pt_xy, void* stream);
+
 /* ---- time of impact: when body pairs first touch along the engine's move, differentiable ----
  * A step accepts a move whose END pose does not penetrate; a body that travels more than an obstacle's thickness in one dt lands
  * beyond it without a record.  This query says when P pairs per scene first come within a margin of each other along the move, for

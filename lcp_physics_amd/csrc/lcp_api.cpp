@@ -877,6 +877,39 @@ int lcp_pair_distance_backward_f64(int B, int nb, int nvcap, int scene_verts_max
                                             pair_second, pair_max_dist, g_dist, g_p, g_radius, g_verts_local, stream);
 }
 
+// what both point-probe entries refuse before any launch: a negative batch, sizes outside the packed vertex list's, a point count
+// outside 1..1024, a missing scene or point array
+static bool point_distance_args_ok(int B, int nb, int nvcap, int scene_verts_max, int N, const void* kind, const void* radius,
+                                   const void* verts_local, const void* nverts, const void* p, const void* pt_body, const void* pt_xy,
+                                   const void* pt_target, const void* pt_max_dist) {
+  if (B < 0 || !lcp::point_distance_supported(nb, nvcap, scene_verts_max, N)) return false;
+  return kind && radius && verts_local && nverts && p && pt_body && pt_xy && pt_target && pt_max_dist;
+}
+
+int lcp_point_distance_f64(int B, int nb, int nvcap, int scene_verts_max, int N, const int32_t* kind, const double* radius,
+                           const double* verts_local, const int32_t* nverts, const double* p, const int32_t* pt_body,
+                           const double* pt_xy, const int32_t* pt_target, const double* pt_max_dist, double* dist, int32_t* body,
+                           double* normal, void* stream) {
+  if (!point_distance_args_ok(B, nb, nvcap, scene_verts_max, N, kind, radius, verts_local, nverts, p, pt_body, pt_xy, pt_target, pt_max_dist))
+    return LCP_E_BADARG;
+  if (!dist && !body && !normal) return LCP_E_BADARG;                 // (nothing asked for)
+  if (B == 0) return 0;
+  return lcp::point_distance_launch(B, nb, nvcap, scene_verts_max, N, kind, radius, verts_local, nverts, p, pt_body, pt_xy, pt_target,
+                                    pt_max_dist, dist, body, normal, stream);
+}
+
+int lcp_point_distance_backward_f64(int B, int nb, int nvcap, int scene_verts_max, int N, const int32_t* kind, const double* radius,
+                                    const double* verts_local, const int32_t* nverts, const double* p, const int32_t* pt_body,
+                                    const double* pt_xy, const int32_t* pt_target, const double* pt_max_dist, const double* g_dist,
+                                    double* g_p, double* g_radius, double* g_verts_local, double* g_pt_xy, void* stream) {
+  if (!point_distance_args_ok(B, nb, nvcap, scene_verts_max, N, kind, radius, verts_local, nverts, p, pt_body, pt_xy, pt_target, pt_max_dist))
+    return LCP_E_BADARG;
+  if (!g_dist || (!g_p && !g_radius && !g_verts_local && !g_pt_xy)) return LCP_E_BADARG;
+  if (B == 0) return 0;
+  return lcp::point_distance_backward_launch(B, nb, nvcap, scene_verts_max, N, kind, radius, verts_local, nverts, p, pt_body, pt_xy,
+                                             pt_target, pt_max_dist, g_dist, g_p, g_radius, g_verts_local, g_pt_xy, stream);
+}
+
 // what both time-of-impact entries refuse before any launch: what the proximity entries refuse, with the velocities among the scene arrays
 static bool time_of_impact_args_ok(int B, int nb, int nvcap, int scene_verts_max, int P, const void* kind, const void* radius,
                                    const void* verts_local, const void* nverts, const void* p, const void* v, const void* pair_first,

@@ -312,6 +312,18 @@ int pair_distance_backward_launch(int B, int nb, int nvcap, int scene_verts_max,
                                   const int32_t* pair_second, const double* pair_max_dist, const double* g_dist, double* g_p,
                                   double* g_radius, double* g_verts_local, void* stream);
 
+// lcp_points.hip: the signed distance from query points to the scene (include/lcp_hip.h, "point probes") and the backward of the
+// distances; arguments checked by the caller
+bool point_distance_supported(int nb, int nvcap, int scene_verts_max, int N);     // render_supported and 1 <= N <= 1024
+int point_distance_launch(int B, int nb, int nvcap, int scene_verts_max, int N, const int32_t* kind, const double* radius,
+                          const double* verts_local, const int32_t* nverts, const double* p, const int32_t* pt_body,
+                          const double* pt_xy, const int32_t* pt_target, const double* pt_max_dist, double* dist, int32_t* body,
+                          double* normal, void* stream);
+int point_distance_backward_launch(int B, int nb, int nvcap, int scene_verts_max, int N, const int32_t* kind, const double* radius,
+                                   const double* verts_local, const int32_t* nverts, const double* p, const int32_t* pt_body,
+                                   const double* pt_xy, const int32_t* pt_target, const double* pt_max_dist, const double* g_dist,
+                                   double* g_p, double* g_radius, double* g_verts_local, double* g_pt_xy, void* stream);
+
 // lcp_toi.hip: the time of impact of body pairs along the move p + t v (include/lcp_hip.h, "time of impact") and the backward of the
 // times; arguments checked by the caller
 bool time_of_impact_supported(int nb, int nvcap, int scene_verts_max, int P);     // render_supported and 1 <= P <= 1024

@@ -1147,6 +1147,13 @@ class ContactWorld:
         from .proximity import pair_distances
         return pair_distances(self.geom, self.p, pairs, **kw)
 
+    def probe(self, points, **kw):
+        """The signed distance from the query points of every scene to its bodies, `dist [B,N]` f64 and `body [B,N]` int32
+        (`physics.points.point_distances(self.geom, self.p, points, **kw)`; `normals=True` adds d(dist)/dx), at the pose `render`
+        draws.  After `step(differentiable=True)` the distances are part of the roll-out's graph."""
+        from .points import point_distances
+        return point_distances(self.geom, self.p, points, **kw)
+
     def time_to_contact(self, pairs, horizon=None, **kw):
         """When the body pairs of every scene first touch if every body keeps its velocity, `(toi [B,P] f64, status [B,P] int32)`
         (`physics.impact.time_of_impact(self.geom, self.p, self.v, pairs, horizon, **kw)`; `horizon` defaults to `dt`).  After
