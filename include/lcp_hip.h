@@ -774,6 +774,84 @@ int lcp_pair_distance_backward_f64(int B, int nb, int nvcap, int scene_verts_max
                                    const double* g_dist,
                                    double* g_p, double* g_radius, double* g_verts_local, void* stream);
 
+/* ---- overlap queries: the area of the intersection of body pairs, differentiable ----
+ * How much two bodies overlap, as an area, for P pairs per scene and B scenes in one launch (lcp_overlap.hip).  The area of the
+ * intersection of two convex shapes is C1 in the pose, 0 where the bodies are apart, and grows smoothly from the first touch;
+ * lcp_pair_distance_f64 answers an overlapping pair with the depth of one feature pair, which is only piecewise smooth.  The scene
+ * inputs, their limits and the world vertices w_i, edges e_i = w_i+1 - w_i and outward unit normals n_i are exactly those of
+ * lcp_pair_distance_f64, and so are the pairs: pair_first[B,P] i32 (body 1), pair_second[B,P] i32 (body 2).  The pair set's cutoff
+ * (pair_max_dist) is not an argument and is not consulted: an area needs none.  no_contact is not consulted.
+ *   per pair: area[B,P] f64 >= 0, the area of body 1 n body 2 (a sum that rounds below 0 is returned as 0).
+ *       circle - circle   d = |c2 - c1|.  d >= r1 + r2: 0.  d <= |r1 - r2|: pi min(r1, r2)^2.  Otherwise the lens
+ *               r1^2 acos((d^2 + r1^2 - r2^2) / (2 d r1)) + r2^2 acos((d^2 + r2^2 - r1^2) / (2 d r2))
+ *                   - sqrt((-d + r1 + r2)(d + r1 - r2)(d - r1 + r2)(d + r1 + r2)) / 2,  the acos arguments clamped to [-1, 1].
+ *       hull A (1) - hull B (2)   Green's theorem over the pieces of either boundary that lie inside the other shape; no intersection
+ *               polygon is built.  Every edge a_i + t e_i of A is clipped against B's half-planes h_j(x) = n^B_j . (x - b_j)
+ *               (Cyrus-Beck), starting from [t0, t1] = [0, 1], and a piece that is left adds cross(p - o, q - o) / 2 = (t1 - t0)
+ *               cross(a_i - o, e_i) / 2 with p = a(t0), q = a(t1) and o = c1, body 1's centre: the terms stay of the bodies' own size
+ *               at coordinates of several hundred.  Then B's edges against A's half-planes.  The terms are about c1, not about the
+ *               overlap, so pieces of the two boundaries that cancel or complement each other have to end in the same point; what
+ *               an edge i of A and an edge j of B have to do with each other is therefore formed ONCE, in one way, whichever of the
+ *               two is being clipped:
+ *                   c = cross(e_i, e^B_j) (two rounded products, no fused multiply-add);  h = n^B_j . (a_i - b_j);
+ *                   parallel: |c| <= 1e-12 |e_i| |e^B_j|;  eps = 64 * 2^-52 (|a_i.x| + |a_i.y| + |b_j.x| + |b_j.y|).
+ *               Not parallel: the two lines cross at X = a_i + tx e_i, tx = -h / (c / |e^B_j|).  A's edge: c > 0: t1 = min(t1, tx),
+ *                   c < 0: t0 = max(t0, tx).  B's edge: t = (X - b_j) . e^B_j / |e^B_j|^2; c > 0: t0 = max(t0, t), c < 0: t1 = min(t1, t).
+ *               Parallel (h stands for the whole edge): A's edge is out when h > eps, and when |h| <= eps and e_i . e^B_j <= 0 (the
+ *                   edges lie on one line and run against each other: the bodies touch from outside there).  B's edge is out unless it
+ *                   lies strictly inside A's half-plane: unless h > eps when e_i . e^B_j > 0, unless h < -eps otherwise.
+ *               A's edge is out when t0 > t1 (closed), B's when t0 >= t1 (open).  Of two edges on one line that run in the same
+ *               direction exactly one is counted - a body inside another with an edge on one of its edges, two identical bodies at
+ *               one pose - and of two that run against each other both or none, at any rotation.  Within the two bands the area is
+ *               off by at most eps or 1e-12 |e| times the edge's length (1e-9 at edges of 30 and coordinates of 500); it is
+ *               continuous across them to the same amount.
+ *       circle - hull, in either order   the sum over the hull's edges: u = w_i - c, the edge u + t e_i split at its crossings of the
+ *               circle, the roots in (0, 1) of |u + t e_i|^2 = r^2, used only when the discriminant is > 0.  A piece whose midpoint
+ *               is within r (<=) adds cross(p, q) / 2, a piece outside adds r^2 atan2(cross(p, q), p . q) / 2 (p, q its ends).  When
+ *               no piece of any edge is within r the area is pi r^2 if the centre lies in the hull (n_i . (c - w_i) <= 0 for every
+ *               i) and exactly 0 otherwise.
+ *   invalid: pair_first == pair_second, an index outside [0, nb), or a hull of fewer than three vertices: area = 0.
+ *   cull:    a pair whose bounding circles (the staged ones, which only over-estimate) do not meet is not evaluated and returns
+ *            exactly 0, which is what the rule gives it; no result depends on the cull.
+ *   a scene with more hull vertices than scene_verts_max is not queried: every pair returns 0.
+ *   out: area[B,P] f64, required; written, never accumulated.
+ * Sizes: those of lcp_pair_distance_f64 (1 <= nb <= 64, 8 <= nvcap <= 64, 0 <= scene_verts_max <= 1024, 1 <= P <= 1024), B >= 0; a
+ * NULL scene or pair array, no output - anything else is LCP_E_BADARG before any launch.  B == 0: success, no launch.  fp64
+ * arithmetic.  One workgroup per (scene, 256 pairs), lane = pair, the cull decided before the pair's loops; a hull pair costs
+ * 2 nA nB half-plane tests and no per-lane arrays.  No allocation, no synchronisation, no global state. */
+int lcp_pair_overlap_f64(int B, int nb, int nvcap, int scene_verts_max, int P,
+                         const int32_t* kind, const double* radius, const double* verts_local, const int32_t* nverts,
+                         const double* p,
+                         const int32_t* pair_first, const int32_t* pair_second,
+                         double* area, void* stream);
+
+/* Backward of lcp_pair_overlap_f64.  Same inputs and checks; nothing is saved by the forward, every pair is recomputed.
+ *   in: g_area[B,P] f64 (required).
+ *   out (each optional, at least one; written, never accumulated): g_p[B,nb,3] f64, g_radius[B,nb] f64 (hulls: 0),
+ *       g_verts_local[B,nb,nvcap,2] f64 (body frame; circles and slots >= nverts: 0).
+ * Only the pieces of a body's own boundary that lie inside the other body move the area:
+ *       d(area) = sum over the pieces of  integral n . dW ds
+ *   a piece [t0, t1] of a hull's edge i (the pieces of the forward):  |e_i| n_i . [((t1 - t0) - s) dw_i + s dw_i+1], s = (t1^2 - t0^2) / 2,
+ *       with dw = dc + drot perp(w - c) + R(rot) dv_local, perp(x, y) = (-y, x), the material motion of "proximity queries";
+ *   a circle against a hull: by translation invariance its centre receives minus what the pieces of the hull's edges within r give
+ *       the hull's translation, -sum |e_i| n_i (t1 - t0); its radius r times the angle of its arc inside the hull, the sum of the
+ *       atan2 terms of the pieces outside (2 pi when the whole circle lies in the hull);
+ *   circle - circle (the lens): with alpha_k the acos of circle k and nhat = (c2 - c1) / d, d(area)/dc1 = chord nhat = -d(area)/dc2,
+ *       chord = 2 r1 sin alpha_1, and d(area)/dr_k = 2 alpha_k r_k; one circle inside the other: 2 pi r for the smaller one (body 1
+ *       when the radii are equal), nothing else.
+ * The motion of the clip parameters cancels between the two pieces that meet in a crossing.  A pair whose bodies are apart has zero
+ * gradient (the forward returns a sum that rounds below 0 as 0; the backward does not look at the sum).
+ * Where a piece of one boundary lies exactly in the other's the area has a kink and this is one of its one-sided differentials.
+ * One workgroup per scene; a body's gradient comes from its own boundary alone, so nothing per pair is staged: every body is owned by
+ * one wavefront that takes the pairs the body is part of in pair order, lane = the body's edge (a circle: the partner's edge), and
+ * sums in registers - no atomics, two runs give the same bits. */
+int lcp_pair_overlap_backward_f64(int B, int nb, int nvcap, int scene_verts_max, int P,
+                                  const int32_t* kind, const double* radius, const double* verts_local, const int32_t* nverts,
+                                  const double* p,
+                                  const int32_t* pair_first, const int32_t* pair_second,
+                                  const double* g_area,
+                                  double* g_p, double* g_radius, double* g_verts_local, void* stream);
+
 /* ---- point probes: the signed distance from query points to the scene, differentiable ----
  * How far a point is from the scene - negative inside a body - and from which body, for N points per scene and B scenes in one
  * launch (lcp_points.hip).  A point is mounted on a body (or on the world frame) and tests every other body or one target body.  The

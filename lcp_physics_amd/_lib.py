@@ -92,6 +92,9 @@ SIGNATURES = {
     # the proximity queries: sizes, the scene, the pairs (first, second, max_dist), then the outputs
     "lcp_pair_distance_f64": (_I, [_I] * 5 + [_P] * 5 + [_P] * 3 + [_P] * 4 + [_P]),
     "lcp_pair_distance_backward_f64": (_I, [_I] * 5 + [_P] * 5 + [_P] * 3 + [_P] + [_P] * 3 + [_P]),
+    # the overlap queries: sizes, the scene, the pairs (first, second), then area / g_area and the gradients
+    "lcp_pair_overlap_f64": (_I, [_I] * 5 + [_P] * 5 + [_P] * 2 + [_P] + [_P]),
+    "lcp_pair_overlap_backward_f64": (_I, [_I] * 5 + [_P] * 5 + [_P] * 2 + [_P] + [_P] * 3 + [_P]),
     # the point probes: sizes, the scene, the points (body, xy, target, max_dist), then the outputs
     "lcp_point_distance_f64": (_I, [_I] * 5 + [_P] * 5 + [_P] * 4 + [_P] * 3 + [_P]),
     "lcp_point_distance_backward_f64": (_I, [_I] * 5 + [_P] * 5 + [_P] * 4 + [_P] + [_P] * 4 + [_P]),

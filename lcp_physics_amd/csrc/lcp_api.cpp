@@ -877,6 +877,37 @@ int lcp_pair_distance_backward_f64(int B, int nb, int nvcap, int scene_verts_max
                                             pair_second, pair_max_dist, g_dist, g_p, g_radius, g_verts_local, stream);
 }
 
+// what both overlap entries refuse before any launch: what the proximity entries refuse, without a cutoff among the pair arrays
+static bool pair_overlap_args_ok(int B, int nb, int nvcap, int scene_verts_max, int P, const void* kind, const void* radius,
+                                 const void* verts_local, const void* nverts, const void* p, const void* pair_first,
+                                 const void* pair_second) {
+  if (B < 0 || !lcp::pair_overlap_supported(nb, nvcap, scene_verts_max, P)) return false;
+  return kind && radius && verts_local && nverts && p && pair_first && pair_second;
+}
+
+int lcp_pair_overlap_f64(int B, int nb, int nvcap, int scene_verts_max, int P, const int32_t* kind, const double* radius,
+                         const double* verts_local, const int32_t* nverts, const double* p, const int32_t* pair_first,
+                         const int32_t* pair_second, double* area, void* stream) {
+  if (!pair_overlap_args_ok(B, nb, nvcap, scene_verts_max, P, kind, radius, verts_local, nverts, p, pair_first, pair_second))
+    return LCP_E_BADARG;
+  if (!area) return LCP_E_BADARG;
+  if (B == 0) return 0;
+  return lcp::pair_overlap_launch(B, nb, nvcap, scene_verts_max, P, kind, radius, verts_local, nverts, p, pair_first, pair_second, area,
+                                  stream);
+}
+
+int lcp_pair_overlap_backward_f64(int B, int nb, int nvcap, int scene_verts_max, int P, const int32_t* kind, const double* radius,
+                                  const double* verts_local, const int32_t* nverts, const double* p, const int32_t* pair_first,
+                                  const int32_t* pair_second, const double* g_area, double* g_p, double* g_radius,
+                                  double* g_verts_local, void* stream) {
+  if (!pair_overlap_args_ok(B, nb, nvcap, scene_verts_max, P, kind, radius, verts_local, nverts, p, pair_first, pair_second))
+    return LCP_E_BADARG;
+  if (!g_area || (!g_p && !g_radius && !g_verts_local)) return LCP_E_BADARG;
+  if (B == 0) return 0;
+  return lcp::pair_overlap_backward_launch(B, nb, nvcap, scene_verts_max, P, kind, radius, verts_local, nverts, p, pair_first,
+                                           pair_second, g_area, g_p, g_radius, g_verts_local, stream);
+}
+
 // what both point-probe entries refuse before any launch: a negative batch, sizes outside the packed vertex list's, a point count
 // outside 1..1024, a missing scene or point array
 static bool point_distance_args_ok(int B, int nb, int nvcap, int scene_verts_max, int N, const void* kind, const void* radius,

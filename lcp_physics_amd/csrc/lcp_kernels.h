@@ -312,6 +312,17 @@ int pair_distance_backward_launch(int B, int nb, int nvcap, int scene_verts_max,
                                   const int32_t* pair_second, const double* pair_max_dist, const double* g_dist, double* g_p,
                                   double* g_radius, double* g_verts_local, void* stream);
 
+// lcp_overlap.hip: the area of the intersection of body pairs (include/lcp_hip.h, "overlap queries") and its backward; arguments
+// checked by the caller
+bool pair_overlap_supported(int nb, int nvcap, int scene_verts_max, int P);       // render_supported and 1 <= P <= 1024
+int pair_overlap_launch(int B, int nb, int nvcap, int scene_verts_max, int P, const int32_t* kind, const double* radius,
+                        const double* verts_local, const int32_t* nverts, const double* p, const int32_t* pair_first,
+                        const int32_t* pair_second, double* area, void* stream);
+int pair_overlap_backward_launch(int B, int nb, int nvcap, int scene_verts_max, int P, const int32_t* kind, const double* radius,
+                                 const double* verts_local, const int32_t* nverts, const double* p, const int32_t* pair_first,
+                                 const int32_t* pair_second, const double* g_area, double* g_p, double* g_radius,
+                                 double* g_verts_local, void* stream);
+
 // lcp_points.hip: the signed distance from query points to the scene (include/lcp_hip.h, "point probes") and the backward of the
 // distances; arguments checked by the caller
 bool point_distance_supported(int nb, int nvcap, int scene_verts_max, int N);     // render_supported and 1 <= N <= 1024

@@ -1147,6 +1147,13 @@ class ContactWorld:
         from .proximity import pair_distances
         return pair_distances(self.geom, self.p, pairs, **kw)
 
+    def overlap(self, pairs, **kw):
+        """The intersection area of the body pairs of every scene, `area [B,P]` f64 (`physics.overlap.pair_overlaps(self.geom, self.p,
+        pairs, **kw)`; `iou=True` adds area / union), at the pose `render` draws - a goal zone that `geom.no_contact` keeps out of
+        collisions is a body like any other here.  After `step(differentiable=True)` the areas are part of the roll-out's graph."""
+        from .overlap import pair_overlaps
+        return pair_overlaps(self.geom, self.p, pairs, **kw)
+
     def probe(self, points, **kw):
         """The signed distance from the query points of every scene to its bodies, `dist [B,N]` f64 and `body [B,N]` int32
         (`physics.points.point_distances(self.geom, self.p, points, **kw)`; `normals=True` adds d(dist)/dx), at the pose `render`

@@ -6,7 +6,8 @@ import json, os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "lcp_physics_amd", "csrc")
 FILES = {"lcp_quad.hip": ["-fno-slp-vectorize"], "lcp_quad_n15e3.hip": ["-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=max-memory-clause"], "lcp_quad_n9e3.hip": ["-fno-slp-vectorize"], "lcp_quad_n12e3.hip": ["-fno-slp-vectorize"], "lcp_quad_n6e3.hip": ["-fno-slp-vectorize"],
-         "lcp_solo.hip": ["-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=iterative-ilp"], "lcp_big.hip": [], "lcp_primal.hip": [], "lcp_primal_pin.hip": [], "lcp_primal_chain.hip": [], "lcp_primal_poststab.hip": [], "lcp_primal_wg.hip": [], "lcp_primal_wg_poststab.hip": [], "lcp_wave64.hip": [], "lcp_generic.hip": [], "lcp_contacts.hip": []}
+         "lcp_solo.hip": ["-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=iterative-ilp"], "lcp_big.hip": [], "lcp_primal.hip": [], "lcp_primal_pin.hip": [], "lcp_primal_chain.hip": [], "lcp_primal_poststab.hip": [], "lcp_primal_wg.hip": [], "lcp_primal_wg_poststab.hip": [], "lcp_wave64.hip": [], "lcp_generic.hip": [], "lcp_contacts.hip": [],
+         "lcp_overlap.hip": []}
 KEYS = {"VGPRs": "vgpr", "AGPRs": "agpr", "ScratchSize [bytes/lane]": "scratch_bytes_per_lane",
         "Occupancy [waves/SIMD]": "occupancy_waves_per_simd", "LDS Size [bytes/block]": "lds_static_bytes",
         "VGPRs Spill": "vgpr_spills", "SGPRs Spill": "sgpr_spills", "TotalSGPRs": "sgpr"}
@@ -59,6 +60,8 @@ def main():
         "lcp_classify_big": pick("lcp_classify_big"),
         "lcp_primal_kernel_40_fwd": pick("lcp_primal_kernel<40, false, false, 4, 0>"),           # the general form (36 x 36 on config 5)
         "lcp_primal_kernel_40_bwd": pick("lcp_primal_kernel<40, true, false, 4, 0>"),
+        "lcp_pair_overlap_fwd": pick("lcp_pair_overlap_kernel"),                                 # the overlap queries: lane = pair
+        "lcp_pair_overlap_bwd": pick("lcp_pair_overlap_backward_kernel"),                        # ... lane = edge, a body per wavefront
         "all_kernels": nice,
         "source": "hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage (tools/kernel_resources.py)",
     }
