@@ -884,6 +884,33 @@ __device__ __forceinline__ void row16(const TI* row, int nz, TI (&out)[16]) {
     else out[J] = row[J < nz ? J : 0];
   });
 }
+// Round 13 (profiles/r13_ab_prologue.txt) - what the stretch before the first multiplication spends in LDS, each one flag away from the old form:
+//   LCP_Q_LDS_ROW128   a lane's 16-entry row goes to its LDS copy (GL / GTL / AtL: row-major, 64 bytes per lane in fp32) as 16-byte stores.
+//                      As dwords the sixteen lanes of a scene hit two banks; a 16-byte store is served eight lanes at a time, four banks each.
+//   LCP_Q_ROWS_SELECT  assemble_q of the forward with a full contact list at compile time (NCF == 16) puts the lane's rows together in
+//                      registers (selects on the contact's two body indices) - no zero-fill, no scatter, no read-back
+#ifndef LCP_Q_LDS_ROW128
+#define LCP_Q_LDS_ROW128 1
+#endif
+#ifndef LCP_Q_ROWS_SELECT
+#define LCP_Q_ROWS_SELECT 1
+#endif
+// dst: 16 entries of a scene's row-major block, 16-byte aligned (carve_q hands out multiples of 16 bytes, a row is 16 entries)
+template <typename TI>
+__device__ __forceinline__ void lds_row16(TI* dst, const TI* v) {
+#if LCP_Q_LDS_ROW128
+  constexpr int PER = 16 / (int)sizeof(TI);
+  typedef TI Piece __attribute__((ext_vector_type(PER)));
+  static_for<16 / PER>([&](auto K_) LCP_INL {
+    constexpr int K = K_;
+    Piece t;
+    static_for<PER>([&](auto I_) LCP_INL { constexpr int I = I_; t[I] = v[K * PER + I]; });
+    *(Piece*)(dst + K * PER) = t;
+  });
+#else
+  static_for<16>([&](auto J_) LCP_INL { constexpr int J = J_; dst[J] = v[J]; });
+#endif
+}
 // dense contact-structured LCP -> per-lane rows (+ LDS copies for the transposed products)
 template <typename TI, typename TC, typename SQ>
 __device__ __forceinline__ void load_dense_q(SQ& S, const FwdArgs& P, const Ws<TI, TC>& W, int scene,
@@ -927,8 +954,8 @@ __device__ __forceinline__ void load_dense_q(SQ& S, const FwdArgs& P, const Ws<T
 // coefficient are ZERO here: every tangential term of the products and of the formation then adds an exact zero, the m-space statements
 // of the kernel take the .n components only), p = 0, h = gc = Jc v + Jc v * -restitutions (:87-89), b = ge = Je v (:86, formed by the
 // caller once the A rows are in LDS)
-template <typename TI, typename TC, int XH, typename SQ, bool POST = false>
-__device__ __forceinline__ void assemble_q(SQ& S, const StepArgs& P, int scene, XV<TC, XH>& p, TC& hn, TC& b) {
+template <typename TI, typename TC, int XH, typename SQ, bool POST = false, bool RSEL = false>
+__device__ __forceinline__ void assemble_q(SQ& S, const StepArgs& P, int scene, XV<TC, XH>& p, TC& hn, TC& b LCP_QSTAMP_ARG) {
   constexpr int RS = 16 * XH;
   const int nb = P.nb, nc = S.ncap, nz = S.nz, e = S.e, l16 = S.l16;
   const bool vc = l16 < S.nc;
@@ -963,20 +990,44 @@ __device__ __forceinline__ void assemble_q(SQ& S, const StepArgs& P, int scene, 
   // 213-224) is staged in LDS - in the scene's still unused rows of GL - and gathered from there: the gathers no longer wait for a second
   // round trip to HBM behind the index loads (2 000 cycles of a 10 000-cycle prologue, one wavefront per SIMD).  The 16 lanes of a scene are
   // lanes of ONE wavefront and the LDS serves a wavefront's accesses in order: no barrier between the staging stores and the gathers.
+  LCP_QSTAMP(st, 0)                                                       // every global load issued
+  LCP_QSTAMP_W(st, 1)                                                     // ... and arrived
   TI* const stage = S.L.GL;
   static_for<XH>([&](auto HX) LCP_INL { const int j = 16 * HX + l16; if (j < nz) stage[j] = vvj[HX]; });
   if (l16 < nb) { stage[2 * RS + l16] = rest_l; stage[3 * RS + l16] = fric_l; }
   pin_vgpr(rnx); pin_vgpr(rny); pin_vgpr(r1x); pin_vgpr(r1y); pin_vgpr(r2x); pin_vgpr(r2y); pin_vgpr(rb1); pin_vgpr(rb2);
   ContactRows<TI> r = {};
   if (vc) r = make_contact_rec<TI>(rnx, rny, r1x, r1y, r2x, r2y, rb1, rb2, stage + 2 * RS, stage + 3 * RS, stage);
-  static_for<RS>([&](auto J) LCP_INL { S.L.GL[l16 * RS + J] = (TI)0; S.L.GTL[l16 * RS + J] = (TI)0; });
-  if (vc) {
+  LCP_QSTAMP_W(st, 2)                                                     // contact records built (staged, gathered)
+  // RSEL (LCP_Q_ROWS_SELECT): the lane's rows of Jc / Jt are put together in REGISTERS - entry 3 b + q is the contact's q-th entry for body
+  // b1 or b2, zero elsewhere; b2 wins where the two name one body, as the second store of the scatter below did - and go to their LDS
+  // copies as whole rows.  The zero-fill, the scatter behind it and the read-back of the row were 76 dword accesses at a 64-byte lane
+  // stride (two banks for the sixteen lanes of a scene) and two more dependent LDS trips in front of the first multiplication
+  // (profiles/r13_ab_prologue.txt).  Asked for ONLY by the forward whose sixteen lanes all own a contact at compile time (NCF == 16, the
+  // headline kernel): `vc` is the constant true there and the selects are 60 v_cndmask.  With a lane-dependent `vc` the compiler turns
+  // the same selects into nested divergent branches with register copies at every join (run-time-count forward 15 / 3: 889 -> 4650
+  // instructions in front of the first v_rcp_f64) - those instantiations keep the scatter.
+  constexpr bool SEL = RSEL && (LCP_Q_ROWS_SELECT != 0) && XH == 1;
+  TI jcr[SEL ? 16 : 1], jtr[SEL ? 16 : 1];
+  if constexpr (SEL) {
+    static_for<16>([&](auto J_) LCP_INL {
+      constexpr int J = J_, BD = J / 3, Q = J % 3;
+      jcr[J] = (vc && r.b2 == BD) ? r.jn[3 + Q] : ((vc && r.b1 == BD) ? r.jn[Q] : (TI)0);
+      jtr[J] = (!POST && vc && r.b2 == BD) ? r.jf[3 + Q] : ((!POST && vc && r.b1 == BD) ? r.jf[Q] : (TI)0);
+    });
+    lds_row16(S.L.GL + l16 * 16, jcr); lds_row16(S.L.GTL + l16 * 16, jtr);
+  } else {
+    static_for<RS>([&](auto J) LCP_INL { S.L.GL[l16 * RS + J] = (TI)0; S.L.GTL[l16 * RS + J] = (TI)0; });
+    if (vc) {
 #pragma unroll
-    for (int q = 0; q < 6; ++q) {
-      const int col = (q < 3) ? 3 * r.b1 + q : 3 * r.b2 + (q - 3);
-      S.L.GL[l16 * RS + col] = r.jn[q];
-      if constexpr (!POST) S.L.GTL[l16 * RS + col] = r.jf[q];
+      for (int q = 0; q < 6; ++q) {
+        const int col = (q < 3) ? 3 * r.b1 + q : 3 * r.b2 + (q - 3);
+        S.L.GL[l16 * RS + col] = r.jn[q];
+        if constexpr (!POST) S.L.GTL[l16 * RS + col] = r.jf[q];
+      }
     }
+  }
+  if (vc) {
     hrow = r.h; mu = POST ? (TI)0 : r.mu;
     hpost = (TC)r.jv + (TC)r.jv * -(TC)r.rbar;                              // engines.py:87-89 (as lcp_poststab_primal_kernel)
   }
@@ -986,12 +1037,22 @@ __device__ __forceinline__ void assemble_q(SQ& S, const StepArgs& P, int scene, 
     static_for<16>([&](auto K) LCP_INL { pin_vgpr(ajr[HX][K]); });
     pin_vgpr(mdj[HX]); pin_vgpr(vvj[HX]); pin_vgpr(ffj[HX]);
   });
-  if constexpr (sizeof(S.jc) == sizeof(TI) * RS)                                                        // (ROWL: the rows stay in LDS)
-    static_for<RS>([&](auto J) LCP_INL { S.jc[J] = S.L.GL[l16 * RS + J]; S.jt[J] = S.L.GTL[l16 * RS + J]; });   // own row only
-  static_for<RS>([&](auto K_) LCP_INL {
-    constexpr int K = K_;
-    if (l16 < EQ) S.L.AtL[l16 * RS + K] = (l16 < e && K < nz) ? ajr[K >> 4][K & 15] : (TI)0;
-  });
+  if constexpr (SEL) {
+    if constexpr (sizeof(S.jc) == sizeof(TI) * RS)                                                      // (ROWL: the rows stay in LDS)
+      static_for<16>([&](auto J) LCP_INL { S.jc[J] = jcr[J]; S.jt[J] = jtr[J]; });
+    if (l16 < EQ) {
+      TI ar[16];
+      static_for<16>([&](auto K) LCP_INL { ar[K] = (l16 < e && K < nz) ? ajr[0][K] : (TI)0; });
+      lds_row16(S.L.AtL + l16 * 16, ar);
+    }
+  } else {
+    if constexpr (sizeof(S.jc) == sizeof(TI) * RS)                                                      // (ROWL: the rows stay in LDS)
+      static_for<RS>([&](auto J) LCP_INL { S.jc[J] = S.L.GL[l16 * RS + J]; S.jt[J] = S.L.GTL[l16 * RS + J]; });   // own row only
+    static_for<RS>([&](auto K_) LCP_INL {
+      constexpr int K = K_;
+      if (l16 < EQ) S.L.AtL[l16 * RS + K] = (l16 < e && K < nz) ? ajr[K >> 4][K & 15] : (TI)0;
+    });
+  }
   static_for<XH>([&](auto HX) LCP_INL {
     const int j = 16 * HX + l16;
     const TI q = (j < nz) ? mdj[HX] : (TI)1;
@@ -1003,6 +1064,7 @@ __device__ __forceinline__ void assemble_q(SQ& S, const StepArgs& P, int scene, 
   S.mu = (TC)mu;
   hn = POST ? hpost : (TC)hrow;
   b = (TC)0;
+  LCP_QSTAMP_W(st, 5)                                                     // rows in registers and in LDS (no global store is under way yet)
 }
 
 // pre_factor_kkt for diagonal Q: G Q^-1 A^T rows, (A Q^-1 A^T)^-1, W = J P J^T into the workspace
@@ -1122,6 +1184,7 @@ __global__ void __launch_bounds__(64, (ALG == 2 ? LCP_Q_OCC2 : 1)) lcp_fwd_quad(
 #ifdef LCP_Q_PROFILE
   const long long prof_t0 = clock64();                  // (the prologue and the whole kernel are in the record too: round 6)
   long long pr_t2 = prof_t0;
+  Stamps st; for (int i = 0; i < 8; ++i) st.t[i] = prof_t0;   // (round 13: the stretch before the loop in six parts, first trips against hot ones)
 #endif
   const int lane = threadIdx.x, l16 = lane & 15, row = lane >> 4;
   const int Btot = FUSED ? SP.B : P.B;
@@ -1162,7 +1225,7 @@ __global__ void __launch_bounds__(64, (ALG == 2 ? LCP_Q_OCC2 : 1)) lcp_fwd_quad(
   XVt p;
   TC hn, b;
   if constexpr (FUSED) {
-    assemble_q<TI, TC, XH, decltype(S), POST>(S, SP, scene, p, hn, b);
+    assemble_q<TI, TC, XH, decltype(S), POST, (NZF > 0 && NCF == 16)>(S, SP, scene, p, hn, b LCP_QSTAMP_PASS);
     if constexpr (!POST) {
       if (live && vc) W.meta[1 + l16] = S.mu;
       if (live && l16 == 0) { W.meta[0] = (TC)2; W.meta[18] = (TC)1; }
@@ -1433,8 +1496,19 @@ __global__ void __launch_bounds__(64, (ALG == 2 ? LCP_Q_OCC2 : 1)) lcp_fwd_quad(
   };
   if constexpr (ALG != 0) {
     if (iteration(std::integral_constant<int, 0>{}, -1)) {
+#ifdef LCP_Q_PROFILE
+      LCP_QSTAMP(st, 3)                                                    // the initialisation pass: a first trip through its code
+      st.t[4] = st.t[3];
+#pragma unroll 1
+      for (int it = 0; it < max_iter; ++it) {
+        const bool more = iteration(std::integral_constant<int, 1>{}, it);
+        if (it == 0) LCP_QSTAMP(st, 4)                                     // iteration 0: the first trip through the loop body
+        if (!more) break;
+      }
+#else
 #pragma unroll 1
       for (int it = 0; it < max_iter; ++it) { if (!iteration(std::integral_constant<int, 1>{}, it)) break; }
+#endif
     }
   } else {
 #pragma unroll 1
@@ -1446,9 +1520,16 @@ __global__ void __launch_bounds__(64, (ALG == 2 ? LCP_Q_OCC2 : 1)) lcp_fwd_quad(
 #undef LCP_Q_BREAK
 #ifdef LCP_Q_PROFILE
   if (!FUSED && P.trace && lane == 0) { double* tr = P.trace + (size_t)scene * 4 * max_iter; for (int i = 0; i < 8; ++i) tr[i] = (double)pr.t[i]; tr[8] = (double)iters; }
-  long long prof_keep[13];                              // (contact-list entry: the record replaces the tail of the wave's first `s` row, below)
+  long long prof_keep[21];                              // (contact-list entry: the record replaces the tail of the wave's first `s` row, below)
   for (int i = 0; i < 8; ++i) prof_keep[i] = pr.t[i];
   prof_keep[8] = iters; prof_keep[9] = prof_prologue; prof_keep[11] = prof_t1 - prof_t0; prof_keep[12] = pr_t2 - prof_t1;
+  // (round 13) 13..15: kernel start -> loads issued -> arrived -> contact records built; 19: -> rows in registers and in LDS.  What is left of
+  // [11] behind these four is the older stamp's own wait for the acknowledgement of the meta stores - vmcnt counts stores - which the kernel
+  // itself never waits for;
+  // 16: loop entry -> end of the initialisation pass, 17: -> end of iteration 0, 18: -> end of the last iteration
+  prof_keep[13] = st.t[0] - prof_t0; prof_keep[14] = st.t[1] - st.t[0]; prof_keep[15] = st.t[2] - st.t[1];
+  prof_keep[16] = st.t[3] - (prof_t0 + prof_prologue); prof_keep[17] = st.t[4] - st.t[3]; prof_keep[18] = pr.last - st.t[4];
+  prof_keep[19] = st.t[5] - st.t[2]; prof_keep[20] = 0;
 #endif
 
   // outputs (natural m-space order: n rows, friction pairs, gamma rows).  The best iterate also goes to the workspace,
@@ -1517,7 +1598,7 @@ __global__ void __launch_bounds__(64, (ALG == 2 ? LCP_Q_OCC2 : 1)) lcp_fwd_quad(
 #ifdef LCP_Q_PROFILE
     __builtin_amdgcn_s_waitcnt(0);
     prof_keep[10] = clock64() - prof_t0;
-    if (lane == 0 && so && m >= 16) { TI* o = so + (size_t)scene * m + (m - 13); for (int i = 0; i < 13; ++i) o[i] = (TI)prof_keep[i]; }
+    if (lane == 0 && so && m >= 24) { TI* o = so + (size_t)scene * m + (m - 21); for (int i = 0; i < 21; ++i) o[i] = (TI)prof_keep[i]; }
 #endif
   } else {
     if (l16 < nz) ((TI*)P.x)[(size_t)scene * nz + l16] = (TI)bx.v[0];
@@ -1648,6 +1729,10 @@ template <typename TI, typename TC, bool BODY = false, int NZF = 0, int EF = 0, 
 __global__ void __launch_bounds__(64) lcp_bwd_quad(BwdArgs P, int lds_per_scene, int accept) {
   static_assert(NZF == 0 || BODY, "compile-time sizes: the body-space backward");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_all[];
+#ifdef LCP_Q_PROFILE
+  const long long prof_t0 = clock64();                  // (round 13: the stretch before the solve and the one behind it, see prof_end)
+  Stamps st; for (int i = 0; i < 8; ++i) st.t[i] = prof_t0;
+#endif
   const int lane = threadIdx.x, l16 = lane & 15, row = lane >> 4;
   const int scene_raw = blockIdx.x * 4 + row;
   const int scene = scene_raw < P.B ? scene_raw : P.B - 1;
@@ -1677,6 +1762,8 @@ __global__ void __launch_bounds__(64) lcp_bwd_quad(BwdArgs P, int lds_per_scene,
   const TC sn_ = W.s[cr], sf1_ = W.s[nc + 2 * cr], sf2_ = W.s[nc + 2 * cr + 1], sg_ = W.s[3 * nc + cr];
   const TI g_ = ((const TI*)P.dl_dx)[(size_t)scene * nz + jx];
   const bool foreign = P.tag && *P.tag != P.tag_value;               // a workspace another kernel family laid out: NaN gradients, not a misread
+  LCP_QSTAMP(st, 0)                                                       // every load issued
+  LCP_QSTAMP_W(st, 1)                                                     // ... and arrived
   const bool live = (scene_raw < P.B) && ((int)meta0 == accept);
   if (!__any(live)) return;
   int ncs = live ? (int)meta19 : 0;                                      // live contacts of the scene (set by the forward)
@@ -1690,11 +1777,13 @@ __global__ void __launch_bounds__(64) lcp_bwd_quad(BwdArgs P, int lds_per_scene,
     static_for<16>([&](auto J) LCP_INL {
       S.jc[J] = (vc && J < nz) ? gj[J] : (TI)0;
       S.jt[J] = (vc && J < nz) ? tj[J] : (TI)0;
-      S.L.GL[l16 * 16 + J] = S.jc[J]; S.L.GTL[l16 * 16 + J] = S.jt[J];
     });
-    static_for<16>([&](auto K) LCP_INL {
-      if (l16 < EQ) S.L.AtL[l16 * 16 + K] = (l16 < e && K < nz) ? aj[K] : (TI)0;
-    });
+    lds_row16(S.L.GL + l16 * 16, S.jc); lds_row16(S.L.GTL + l16 * 16, S.jt);
+    if (l16 < EQ) {
+      TI ar[16];
+      static_for<16>([&](auto K) LCP_INL { ar[K] = (l16 < e && K < nz) ? aj[K] : (TI)0; });
+      lds_row16(S.L.AtL + l16 * 16, ar);
+    }
     if constexpr (!BODY) static_for<EQ>([&](auto A_) LCP_INL {
       S.gan[A_] = gan_[A_]; S.gat[A_] = gat_[A_];
       S.s11row[A_] = (l16 < EQ) ? s11_[A_] : (TC)0;
@@ -1704,6 +1793,7 @@ __global__ void __launch_bounds__(64) lcp_bwd_quad(BwdArgs P, int lds_per_scene,
     S.mu = vc ? mu_ : (TC)0;
   }
   __syncthreads();
+  LCP_QSTAMP_W(st, 2)                                                     // rows staged in LDS, barrier passed
   const TC x = (l16 < nz) ? x_ : (TC)0, y = (l16 < e) ? y_ : (TC)0;
   const M4<TC> z = vc ? m4<TC>(zn_, zf1_, zf2_, zg_) : m4<TC>(1, 1, 1, 1);
   const M4<TC> s = vc ? m4<TC>(sn_, sf1_, sf2_, sg_) : m4<TC>(1, 1, 1, 1);
@@ -1735,6 +1825,16 @@ __global__ void __launch_bounds__(64) lcp_bwd_quad(BwdArgs P, int lds_per_scene,
     solve_kkt_q<TI, TC, 1>(S, ta, tu, R, dinv, vc, g, zero, zero, (TC)0, dxv, ds, dl, dnu, false LCP_QPROF_PASS);  // lcp.py:47-50
     dx = dxv.v[0];
   }
+  LCP_QSTAMP_W(st, 3)                                                     // solve done
+#ifdef LCP_Q_PROFILE
+  // the record of a wave - cycles from the kernel's start to: loads issued, arrived, staged + barrier, solve done, last store issued, end -
+  // over the tail of its first scene's dh row (which this kernel has written by then)
+  auto prof_end = [&]() LCP_INL {
+    LCP_QSTAMP(st, 4)
+    LCP_QSTAMP_W(st, 5)
+    if (lane == 0 && P.dh && m >= 8) { TI* o = (TI*)P.dh + (size_t)scene * m + (m - 6); for (int i = 0; i < 6; ++i) o[i] = (TI)(st.t[i] - prof_t0); }
+  };
+#endif
   if (!live) return;
   // outer products (lcp.py:52-61), one output row per instruction, lanes over the columns
   if (P.dp && l16 < nz) ((TI*)P.dp)[(size_t)scene * nz + l16] = (TI)dx;
@@ -1769,6 +1869,9 @@ __global__ void __launch_bounds__(64) lcp_bwd_quad(BwdArgs P, int lds_per_scene,
         ho[32 + l16] = zq.n; ho[32 + nc + 2 * l16] = zq.f1; ho[32 + nc + 2 * l16 + 1] = zq.f2; ho[32 + 3 * nc + l16] = zq.g;
         ho[32 + 64 + l16] = dl.n; ho[32 + 64 + nc + 2 * l16] = dl.f1; ho[32 + 64 + nc + 2 * l16 + 1] = dl.f2; ho[32 + 64 + 3 * nc + l16] = dl.g;
       }
+#ifdef LCP_Q_PROFILE
+      prof_end();
+#endif
       return;
     }
   }
@@ -1815,6 +1918,9 @@ __global__ void __launch_bounds__(64) lcp_bwd_quad(BwdArgs P, int lds_per_scene,
       }
     });
   }
+#ifdef LCP_Q_PROFILE
+  prof_end();
+#endif
 }
 
 
@@ -1906,7 +2012,10 @@ __global__ void __launch_bounds__(64) lcp_bwd_step_quad(StepArgs SP, StepBwdArgs
   const bool vc = l16 < ncs;
   XVt p_;
   TC hn_, b_;
-  assemble_q<TI, TC, XH>(S, SP, scene, p_, hn_, b_);                      // the same rows the forward solved with
+#ifdef LCP_Q_PROFILE
+  Stamps st;
+#endif
+  assemble_q<TI, TC, XH>(S, SP, scene, p_, hn_, b_ LCP_QSTAMP_PASS);                    // the same rows the forward solved with
   if constexpr (!BODY) static_for<EQ>([&](auto A_) LCP_INL {
     S.gan[A_] = W.GAc[(l16 * 2 + 0) * EQ + A_]; S.gat[A_] = W.GAc[(l16 * 2 + 1) * EQ + A_];
     S.s11row[A_] = (l16 < EQ) ? W.S11i[l16 * EQ + A_] : (TC)0;

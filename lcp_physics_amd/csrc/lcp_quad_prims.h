@@ -144,10 +144,21 @@ struct Prof { long long t[10]; long long last; };
                            (pr).t[i] += now_ - (pr).last; (pr).last = now_; }
 #define LCP_QPROF_ARG , Prof& pr
 #define LCP_QPROF_PASS , pr
+// Stamps of the stretch before the first multiplication (round 13): absolute clock reads, kept on their side of the neighbouring code by
+// scheduling barriers.  LCP_QSTAMP reads the clock as soon as everything before it is ISSUED, LCP_QSTAMP_W once it has ARRIVED as well.
+struct Stamps { long long t[8]; };
+#define LCP_QSTAMP(st, i) { __builtin_amdgcn_sched_barrier(0); (st).t[i] = clock64(); __builtin_amdgcn_sched_barrier(0); }
+#define LCP_QSTAMP_W(st, i) { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_waitcnt(0); (st).t[i] = clock64(); __builtin_amdgcn_sched_barrier(0); }
+#define LCP_QSTAMP_ARG , Stamps& st
+#define LCP_QSTAMP_PASS , st
 #else
 #define LCP_QTICK(pr, i)
 #define LCP_QPROF_ARG
 #define LCP_QPROF_PASS
+#define LCP_QSTAMP(st, i)
+#define LCP_QSTAMP_W(st, i)
+#define LCP_QSTAMP_ARG
+#define LCP_QSTAMP_PASS
 #endif
 
 // a / b for the element-wise quotients of pdipm.py (s / z, -z / dz, rs / s ...).  LCP_Q_FAST_DIV = 1: a x (v_rcp_f64 + two Newton steps)
