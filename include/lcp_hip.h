@@ -1018,6 +1018,48 @@ int lcp_force_elements_backward_f64(int B, int nb, int E,
                                     double* g_p, double* g_v, double* g_k, double* g_c, double* g_x0, double* g_w0,
                                     double* g_a1, double* g_a2, void* stream);
 
+/* ---- mechanism links: rods, slots and sliders between bodies, differentiable ----
+ * Equality rows that are a pure function of the pose, for L links per scene and B scenes in one launch (lcp_links.hip), written
+ * below an optional block of base rows into ONE matrix Je[B, e0 + el, 3 nb] - what the step entries take as `Je`.  Every link is a
+ * position-level function C(p) of the poses p = (rot, x, y); its rows are the exact gradient dC/dp, and the solvers hold Je v = 0.
+ *   pose:    p[B,nb,3] f64.  cross(a, b) = ax by - ay bx, perp(x, y) = (-y, x), R(rot) = [[cos, -sin], [sin, cos]].
+ *   links, [B,L] each (bodies, anchors and angles may differ per scene; the kinds are expected to be the same list in every scene):
+ *            kind i32 (0 none, 1 distance, 2 slot, 3 prismatic), first i32 in [0, nb), second i32 in [-1, nb) (-1: the world),
+ *            a1, a2 [B,L,2] f64 (anchors in the bodies' frames; the world's is a world point), phi f64.
+ *            r_k = R(rot_k) a_k, w_k = c_k + r_k; the world: w_2 = a_2, rot_2 = 0, no columns.
+ *   distance (1), 1 row:  C = |w_2 - w_1| - length, n = (w_2 - w_1) / |w_2 - w_1|
+ *            columns of first (-cross(r_1, n), -n_x, -n_y), of second (cross(r_2, n), n_x, n_y); |w_2 - w_1| < 1e-12: a row of zeros.
+ *   slot (2), 1 row: first's anchor stays on a line fixed in second.  d = w_1 - w_2, t = R(rot_2) (-sin phi, cos phi), C = t . d
+ *            columns of first (cross(r_1, t), t_x, t_y), of second (-cross(r_2 + d, t), -t_x, -t_y).
+ *   prismatic (3), 2 rows: the slot's row, then rot_1 - rot_2 - const: (1, 0, 0) and (-1, 0, 0).
+ *   A link's first row is e0 + the rows of the links before it in ITS scene; a link whose rows would pass `el` is dropped.  kind 0 or
+ *   unknown: no rows.  A link with an index out of range or first == second keeps its rows, all zero.  Rows no link fills are zero.
+ *   out: Je[B, e0 + el, 3 nb] f32, every element written once: rows [0, e0) are Je_base's bits (Je_base[B,e0,3 nb] f32, required when
+ *            e0 > 0, must not overlap Je), link rows are exact zeros but for the six entries, computed in fp64 and rounded once.
+ * Sizes: 1 <= nb <= 64, 1 <= L <= 256, 0 <= e0 <= 65536 (LCP_E_TOOLARGE beyond the upper limits), 0 <= el <= 2 L, B >= 0; a NULL link
+ * array, p or Je, Je_base NULL with e0 > 0 - anything else is LCP_E_BADARG before any launch.  B == 0 or e0 + el == 0: success, no
+ * launch.  A group of lanes per scene (the power of two >= max(nb, L); several scenes share a wavefront below 64), the entries staged
+ * per row in LDS (32 bytes a row), the matrix stored by the whole workgroup with consecutive addresses.  No allocation, no
+ * synchronisation, no global state. */
+int lcp_link_jacobian_f64(int B, int nb, int L, int e0, int el,
+                          const int32_t* kind, const int32_t* first, const int32_t* second,
+                          const double* a1, const double* a2, const double* phi,
+                          const double* p, const float* Je_base, float* Je, void* stream);
+
+/* Backward of the LINK rows of lcp_link_jacobian_f64 (the cotangent of the base rows is gJe's first e0 rows: the caller's slice).
+ * Same inputs and checks; nothing is saved by the forward.
+ *   in: gJe[B, e0 + el, 3 nb] f32 (required), the cotangent of Je.
+ *   out (each optional, at least one; written everywhere, never accumulated; all f64): g_p[B,nb,3], g_a1, g_a2 [B,L,2], g_phi[B,L].
+ *       It includes the derivative of n (distance) and of t and d (slot).  A slot's row does not depend on a2; a distance on phi; the
+ *       second row of a prismatic link is constant.  Links that wrote zeros or nothing: exactly 0.  A body no link names: exactly 0.
+ * Every body's sum is owned by one lane that walks the links in order (staged in LDS, 40 bytes a link): no atomics, two runs give
+ * the same bits, whichever outputs are asked for. */
+int lcp_link_jacobian_backward_f64(int B, int nb, int L, int e0, int el,
+                                   const int32_t* kind, const int32_t* first, const int32_t* second,
+                                   const double* a1, const double* a2, const double* phi,
+                                   const double* p, const float* gJe,
+                                   double* g_p, double* g_a1, double* g_a2, double* g_phi, void* stream);
+
 /* ---- contact reports: the impulses of a solve per body, per body pair and per joint ----
  * Which bodies touch and how hard, from the multipliers a solve wrote (z, y of lcp_solve_dynamics_f32 / lcp_step_fused_f32) and the
  * contact records it consumed, for B scenes in one launch (lcp_report.hip).  The reference's residual is

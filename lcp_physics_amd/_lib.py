@@ -105,6 +105,9 @@ SIGNATURES = {
     # the force elements: sizes, the elements (kind, b1, b2, a1, a2, k, c, x0, w0, limit), p, v, then f_base, f_out / g_f and the gradients
     "lcp_force_elements_f64": (_I, [_I] * 3 + [_P] * 10 + [_P] * 2 + [_P] * 2 + [_P]),
     "lcp_force_elements_backward_f64": (_I, [_I] * 3 + [_P] * 10 + [_P] * 2 + [_P] + [_P] * 8 + [_P]),
+    # the mechanism links: sizes (B, nb, L, e0, el), the links (kind, first, second, a1, a2, phi), p, then Je_base, Je / gJe and the gradients
+    "lcp_link_jacobian_f64": (_I, [_I] * 5 + [_P] * 6 + [_P] + [_P] * 2 + [_P]),
+    "lcp_link_jacobian_backward_f64": (_I, [_I] * 5 + [_P] * 6 + [_P] + [_P] + [_P] * 4 + [_P]),
     # the contact report: sizes, c_count, active, the records, z, y, Je, the pairs, min_impulse, then the seven outputs
     "lcp_contact_report_f32": (_I, [_I] * 5 + [_P] * 2 + [_P] * 5 + [_P] * 3 + [_P] * 2 + [_c.c_double] + [_P] * 7 + [_P]),
     "lcp_extract_params_u8": (_I, [_I] * 3 + [_P] + [_c.c_int64] * 3 + [_P, _I] + [_P] * 8 + [_P]),

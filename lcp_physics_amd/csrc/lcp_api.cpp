@@ -1002,6 +1002,34 @@ int lcp_force_elements_backward_f64(int B, int nb, int E, const int32_t* kind, c
                                              g_w0, g_a1, g_a2, stream);
 }
 
+// what both link entries refuse before any launch (0: nothing): sizes below their lower limits or a missing array (LCP_E_BADARG), sizes
+// beyond the upper limits (LCP_E_TOOLARGE), more link rows than the kinds can have (LCP_E_BADARG)
+static int link_jacobian_args(int B, int nb, int L, int e0, int el, const void* kind, const void* first, const void* second,
+                              const void* a1, const void* a2, const void* phi, const void* p) {
+  if (B < 0 || nb < 1 || L < 1 || e0 < 0 || el < 0) return LCP_E_BADARG;
+  if (!kind || !first || !second || !a1 || !a2 || !phi || !p) return LCP_E_BADARG;
+  if (!lcp::link_jacobian_supported(nb, L, e0)) return LCP_E_TOOLARGE;
+  return el > 2 * L ? LCP_E_BADARG : 0;
+}
+
+int lcp_link_jacobian_f64(int B, int nb, int L, int e0, int el, const int32_t* kind, const int32_t* first, const int32_t* second,
+                          const double* a1, const double* a2, const double* phi, const double* p, const float* Je_base, float* Je,
+                          void* stream) {
+  if (int rc = link_jacobian_args(B, nb, L, e0, el, kind, first, second, a1, a2, phi, p)) return rc;
+  if (!Je || (e0 > 0 && !Je_base)) return LCP_E_BADARG;
+  if (B == 0 || e0 + el == 0) return 0;
+  return lcp::link_jacobian_launch(B, nb, L, e0, el, kind, first, second, a1, a2, phi, p, Je_base, Je, stream);
+}
+
+int lcp_link_jacobian_backward_f64(int B, int nb, int L, int e0, int el, const int32_t* kind, const int32_t* first,
+                                   const int32_t* second, const double* a1, const double* a2, const double* phi, const double* p,
+                                   const float* gJe, double* g_p, double* g_a1, double* g_a2, double* g_phi, void* stream) {
+  if (int rc = link_jacobian_args(B, nb, L, e0, el, kind, first, second, a1, a2, phi, p)) return rc;
+  if (!gJe || (!g_p && !g_a1 && !g_a2 && !g_phi)) return LCP_E_BADARG;
+  if (B == 0) return 0;
+  return lcp::link_jacobian_backward_launch(B, nb, L, e0, el, kind, first, second, a1, a2, phi, p, gJe, g_p, g_a1, g_a2, g_phi, stream);
+}
+
 int lcp_contact_report_f32(int B, int nb, int maxc, int e, int P, const int32_t* c_count, const int32_t* active, const float* c_n,
                            const float* c_p1, const float* c_p2, const int32_t* c_i1, const int32_t* c_i2, const float* z, const float* y,
                            const float* Je, const int32_t* pair_first, const int32_t* pair_second, double min_impulse,

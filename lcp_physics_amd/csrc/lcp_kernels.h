@@ -358,6 +358,15 @@ int force_elements_backward_launch(int B, int nb, int E, const int32_t* kind, co
                                    const double* limit, const double* p, const float* v, const float* g_f, double* g_p, double* g_v,
                                    double* g_k, double* g_c, double* g_x0, double* g_w0, double* g_a1, double* g_a2, void* stream);
 
+// lcp_links.hip: the rows of the mechanism links (include/lcp_hip.h, "mechanism links") and their backward; arguments checked by the caller
+bool link_jacobian_supported(int nb, int L, int e0);                              // 1 <= nb <= 64, 1 <= L <= 256, 0 <= e0 <= 65536
+int link_jacobian_launch(int B, int nb, int L, int e0, int el, const int32_t* kind, const int32_t* first, const int32_t* second,
+                         const double* a1, const double* a2, const double* phi, const double* p, const float* Je_base, float* Je,
+                         void* stream);
+int link_jacobian_backward_launch(int B, int nb, int L, int e0, int el, const int32_t* kind, const int32_t* first, const int32_t* second,
+                                  const double* a1, const double* a2, const double* phi, const double* p, const float* gJe, double* g_p,
+                                  double* g_a1, double* g_a2, double* g_phi, void* stream);
+
 // lcp_report.hip: the contact report (include/lcp_hip.h, "contact reports"); arguments checked by the caller
 bool contact_report_supported(int nb, int maxc, int P);                           // 1 <= nb <= 64, 1 <= maxc <= 1024, 0 <= P <= 1024
 int contact_report_launch(int B, int nb, int maxc, int e, int P, const int32_t* c_count, const int32_t* active, const float* c_n,

@@ -650,12 +650,17 @@ class ContactWorld:
     ordinary short step (`dt_used`), `fixed_dt=True` makes up the remainder in further sub-steps.  `ccd_margin` (default `eps / 2`): the
     distance at which the move ends, within the detection's `eps`, so that the next solve sees the contact.  No gradient through the
     clipped dt.  `time_to_contact(pairs)` is the query itself at the world's `p` and `v`.
+    `links=LinkSet` (physics/links.py) adds rods of fixed length, pins in slots and sliders as equality rows below the others - alone, under
+    a constant `Je` or under a `JointSet`'s rows; `e` counts them all.  Their anchors live in the bodies' frames, so the rows are a function
+    of the pose alone and one launch of `lcp_link_jacobian_f64` rebuilds the combined `Je` wherever the pose has moved (twice per step with
+    `post_stab`); `step(differentiable=True)` differentiates them through the pose, the anchors and the angles.  Held at velocity level
+    like the joints: `links.residual(world.p)` is the drift.
     """
 
     def __init__(self, geom, p, v, Mdiag, f, rest, fric, Je=None, dt=1.0 / 30, eps=0.1, tol=1e-6,
                  strict_no_penetration=True, maxc=16, max_iter=10, compute="f64", solver_eps=1e-12,
                  not_improved_lim=3, max_trials=64, check=True, post_stab=False, force_fn=None, joints=None, broadphase=False,
-                 elements=None, report=None, report_min_impulse=0.0, ccd=None, ccd_margin=None):
+                 elements=None, report=None, report_min_impulse=0.0, ccd=None, ccd_margin=None, links=None):
         from . import contacts as _contacts
         self.post_stab = bool(post_stab)
         # `force_fn(t) -> f [B,nb,3] float32` replaces the constant force: the batched form of the reference's
@@ -710,9 +715,21 @@ class ContactWorld:
         else:
             self.e = eq_rows(Je)
             self.Je = f32(Je) if self.e else None
+        # `links` (a `links.LinkSet`): rods, slots and sliders whose rows follow the pose, appended to the rows above - to none, to a
+        # constant Je or to a JointSet's - by one launch of `lcp_link_jacobian_f64` wherever Je is rebuilt.  `_Je_base` is then what
+        # the links are appended to (the constant rows, or the JointSet's at the current pose); the plain step writes the combined
+        # matrix into the double buffer `Je` / `_Je_spare`, so that a captured graph replays through the same pointers
+        self.links = links
+        self._Je_base = None
+        if links is not None:
+            if links.B != self.B:
+                raise ValueError("links are for %d scenes, the world has %d" % (links.B, self.B))
+            self._Je_base = self.Je
+            self.e += links.e
+            self.Je = links.jacobian(self.p, Je_base=self._Je_base)
         # a constant Je that pins the leading coordinates (the fixed floor of the demo worlds) or no Je at all: LCP_HINT_PINNED,
         # checked once here on the host
-        self._pinned = joints is None and rows_pin_leading_coordinates(self.Je)
+        self._pinned = joints is None and links is None and rows_pin_leading_coordinates(self.Je)
         self.dt, self.eps, self.tol, self.strict = float(dt), float(eps), float(tol), bool(strict_no_penetration)
         self.maxc, self.max_iter, self.compute = int(maxc), int(max_iter), compute
         self.solver_eps, self.lim, self.max_trials = solver_eps, not_improved_lim, max_trials
@@ -794,7 +811,12 @@ class ContactWorld:
         self._p_geom = self._p_geom_src = self._jrot_ad = self._jrot_src = None
         self._drop_graphs()
         pd = self.p.detach()
-        if self.joints is not None:
+        if self.links is not None:
+            if self.joints is not None:
+                self.joints.jrot1.copy_(self._jrot0 if jrot1 is None else jrot1)
+                self._Je_base = self.joints.jacobian(pd)
+            self.Je = self.links.jacobian(pd, Je_base=self._Je_base)
+        elif self.joints is not None:
             self.joints.jrot1.copy_(self._jrot0 if jrot1 is None else jrot1)
             self.Je = self.joints.jacobian(pd)
         self.contacts = self._contacts_mod.find_contacts(self.geom, pd, maxc=self.maxc, eps=self.eps, **self._bp)
@@ -927,7 +949,11 @@ class ContactWorld:
             # kernel's values, the gradient of the torch expression; lcp_step_backward_je_f32 returns dL/dJe
             if self._jrot_src is not self.p:
                 self._jrot_ad, self._jrot_src = js.jrot1.clone(), self.p
-            Je = _JointJacobianFn.apply(self.p, self._jrot_ad, js.jr1, js, self.Je)
+            Je = _JointJacobianFn.apply(self.p, self._jrot_ad, js.jr1, js, self.Je if self.links is None else self._Je_base)
+        elif self.links is not None:
+            Je = self._Je_base
+        if self.links is not None:
+            Je = self._link_node(Je)
         v_new = SolveDynamicsFunction.apply(self.Mdiag, self.v.contiguous(), f, self.rest, self.fric, c_n, c_p1, c_p2, frame.c_i1,
                                             frame.c_i2, count, Je, dt_solve, opts)
         if sub is not None:                                                # world.py:87 set_v(new_v): not for a scene that is finished
@@ -942,7 +968,11 @@ class ContactWorld:
                                   dt_scene=self._ccd_dt(v_new.detach().contiguous(), None if sub is None else sub["dt_k"]), **self._bp)
         # the accepted pose: the kernel's value, the gradient of p + v dt_used (a zero rotation increment carries no gradient to the geometry)
         self.v = v_new
-        if js is not None:                                                 # joint.move(dt): rot1 += body1.v[0] dt (constraints.py:39-43)
+        if self.links is not None:                                         # (fresh tensors: the ones before belong to this step's graph)
+            if js is not None:
+                self._Je_base = js.jacobian(cb.p_out, v=v_new.detach().contiguous(), dt_scene=cb.dt_used)
+            self.Je = self.links.jacobian(cb.p_out, Je_base=self._Je_base)
+        elif js is not None:                                               # joint.move(dt): rot1 += body1.v[0] dt (constraints.py:39-43)
             self.Je = js.jacobian(cb.p_out, v=v_new.detach().contiguous(), dt_scene=cb.dt_used)
         self._record_move(p_geo, v_new, cb.p_out, cb.dt_used, 1.0)
         if self.post_stab:
@@ -953,14 +983,21 @@ class ContactWorld:
             dt_used = cb.dt_used
             g_n, g_p1, g_p2 = ct.ContactFrameFunction.apply(self._p_geom, self.geom, frame2, self.eps, *shape_in)
             pose_dep = js is not None and js.pose_dependent
-            Je2 = _JointJacobianFn.apply(self.p, self._jrot_ad, js.jr1, js, self.Je) if pose_dep else self.Je
+            if self.links is None:
+                Je2 = _JointJacobianFn.apply(self.p, self._jrot_ad, js.jr1, js, self.Je) if pose_dep else self.Je
+            else:
+                Je2 = self._link_node(_JointJacobianFn.apply(self.p, self._jrot_ad, js.jr1, js, self._Je_base) if pose_dep else self._Je_base)
             p_corr = torch.empty_like(cb.p_out)                            # the corrected pose: the kernel's own move, as in step()
             opts["ps_pose"] = (cb.p_out, dt_used, p_corr)
             dp_s = PostStabilizationFunction.apply(self.Mdiag, v_new.contiguous(), self.rest, g_n, g_p1, g_p2, frame2.c_i1, frame2.c_i2,
                                                    frame2.count, Je2, opts)
             ps = opts["last_post_stab"]
             torch.bitwise_or(self.sticky_status, ps["status"], out=self.sticky_status)
-            if js is not None:                                             # the joints follow the correction move (world.py:112-116)
+            if self.links is not None:
+                if js is not None:
+                    self._Je_base = js.jacobian(p_corr, v=dp_s.detach().contiguous(), dt_scene=dt_used, vscale=0.5)
+                self.Je = self.links.jacobian(p_corr, Je_base=self._Je_base)
+            elif js is not None:                                           # the joints follow the correction move (world.py:112-116)
                 self.Je = js.jacobian(p_corr, v=dp_s.detach().contiguous(), dt_scene=dt_used, vscale=0.5)
             self._record_move(self._p_geom, dp_s, p_corr, dt_used, 0.5)
             self.contacts = ct.find_contacts(self.geom, p_corr, maxc=self.maxc, eps=self.eps, **self._bp)   # world.py:121
@@ -1088,7 +1125,9 @@ class ContactWorld:
                                                   max_trials=self.max_trials, t=self.t, out=cb,
                                                   dt_scene=self._ccd_dt(self.v, sub["dt_k"] if fixed else None), **self._bp)
         self.p, cb.p_out = cb.p_out, self.p                              # accepted pose becomes the state (double buffer)
-        if self.joints is not None:                                      # joint.move(dt) + the Jacobian at the new pose (world.py:91-92)
+        if self.links is not None:                                       # the links' rows at the new pose, below the (moved) joints'
+            self._link_rows(self.v, cb.dt_used, 1.0)
+        elif self.joints is not None:                                    # joint.move(dt) + the Jacobian at the new pose (world.py:91-92)
             self._Je_spare = self.joints.jacobian(self.p, v=self.v, dt_scene=cb.dt_used, out=self._Je_spare)
             self.Je, self._Je_spare = self._Je_spare, self.Je
         if self.post_stab:                                               # world.py:109-121
@@ -1098,7 +1137,9 @@ class ContactWorld:
                                     self.Je, p=self.p, dt_scene=cb.dt_used, dt=self.dt, p_out=self.p,
                                     compute=self.compute, ws=self._ps_ws, out=self._ps_out)
             self._ps_ws, self._ps_out = ps["ws"], ps
-            if self.joints is not None:                                  # the joints follow the correction move too (world.py:112-116)
+            if self.links is not None:
+                self._link_rows(ps["dp"], cb.dt_used, 0.5)
+            elif self.joints is not None:                                # the joints follow the correction move too (world.py:112-116)
                 self._Je_spare = self.joints.jacobian(self.p, v=ps["dp"], dt_scene=cb.dt_used, vscale=0.5, out=self._Je_spare)
                 self.Je, self._Je_spare = self._Je_spare, self.Je
             self._contacts_mod.find_contacts(self.geom, self.p, maxc=self.maxc, eps=self.eps, out=cb, **self._bp)   # world.py:121
@@ -1106,6 +1147,22 @@ class ContactWorld:
         ret = dict(out)
         ret["v_new"], ret["v_prev"] = self.v, out["v_new"]               # the NEW velocities; the spare buffer holds the old
         return ret
+
+    def _link_rows(self, v, dt_scene, vscale):
+        """A plain step's Je of a world with `links`, at the pose `self.p` the step has just accepted: the JointSet (if any) moves by
+        `vscale v dt_scene` and writes its rows into the persistent `_Je_base`, the links' launch appends theirs into the spare half of
+        the double buffer, and the halves swap - every pointer the same two steps later."""
+        if self.joints is not None:
+            self._Je_base = self.joints.jacobian(self.p, v=v, dt_scene=dt_scene, vscale=vscale, out=self._Je_base)
+        self._Je_spare = self.links.jacobian(self.p, Je_base=self._Je_base, out=self._Je_spare)
+        self.Je, self._Je_spare = self._Je_spare, self.Je
+
+    def _link_node(self, base):
+        """`self.Je` (the combined matrix the kernel wrote at `self.p`) as a node of the graph: `_LinkJacobianFn` on `self.p` itself, the
+        anchors turn analytically; `base`: the node of the rows above the links' (a JointSet's, a constant Je, or None)."""
+        from .links import _LinkJacobianFn
+        ls = self.links
+        return _LinkJacobianFn.apply(self.p, ls.a1, ls.a2, ls.phi, base, ls, self.Je)
 
     def get_v(self):
         return self.v
